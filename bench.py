@@ -7,7 +7,7 @@ Workload (config[2] of BASELINE.json, the one the metric is quoted on): the refe
 (qpos ‖ qvel, the default ObservationSpec of Env.from_xml_path) all-gathered over RCCL once
 per fused chunk.  One bench "step" = one simulation step of the whole global batch.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 from a plain shell: this process starts the N ranks itself as a child ``torch.distributed.run`` (before importing
 torch or touching HIP) and forwards rank 0's line; under torchrun (RANK / WORLD_SIZE set) it is one of the ranks.
@@ -16,6 +16,12 @@ Prints ONE JSON line (rank 0).  ``value`` = env-steps / s of the whole job with 
 in HBM; ``roofline`` prices the dominant kernel (k_step) against HBM with the algorithmic
 bytes of SURVEY.md §8(d); ``cpu_baseline`` times the float64 oracle (a port: the reference's
 own CPU path needs the absent ``mujoco`` wheel) on the host cores for a bounded sample.
+``ms_per_step`` = wall milliseconds of one timed step (``--steps`` of them are timed).
+
+``--dump-outputs DIR`` writes what the timed path returned in its last step: the gathered observation ring of the last timed
+launch (``obs``, [rows, global batch, obs_dim]) and the state after the last timed step (``qpos``, ``qvel``, ``ctrl``, ``qacc``,
+[global batch, n]), float32, as ``DIR/<name>.npy`` (a seeded sample of environments beyond 64 MB).  The inputs (qpos0 start,
+seeded random ctrl) depend on the arguments alone, so two builds can be compared array for array.
 """
 
 from __future__ import annotations
@@ -109,6 +115,30 @@ def _event_pool(torch, n: int):
     return pool
 
 
+DUMP_STATE = ("qpos", "qvel", "ctrl", "qacc")      # --dump-outputs: the state arrays written beside the observation ring
+DUMP_BUDGET_BYTES = 60_000_000                      # --dump-outputs: array bytes in all (64 MB with room for the .npy headers)
+
+
+def dump_outputs(out_dir: str, outputs: dict, batch: int, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Write ``outputs`` (name -> float32 / float64 array whose axis -2 is the environment) as ``out_dir/<name>.npy``.  When they
+    exceed ``budget`` bytes, the same fixed sample of environments (seed 0, sorted) is taken from every array and its global indices
+    are written too (``sample_env_index.npy``, float64), so that two runs with the same arguments write the same elements."""
+    import numpy as np
+
+    per_env = sum(a.nbytes for a in outputs.values()) // batch
+    sample = None
+    if per_env * batch > budget:
+        sample = np.sort(np.random.default_rng(0).choice(batch, size=max(1, budget // per_env), replace=False))
+        outputs = {k: np.take(a, sample, axis=-2) for k, a in outputs.items()}
+        outputs["sample_env_index"] = sample.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+    return {"dir": os.path.abspath(out_dir), "arrays": {k: [str(a.dtype), list(a.shape)] for k, a in outputs.items()},
+            "environments": batch if sample is None else int(sample.size), "sampled": sample is not None}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -129,6 +159,9 @@ def main() -> None:
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal of the multi-process path (observations staged through the host)")
     ap.add_argument("--collective", default="auto", choices=["auto", "rccl", "torch"], help="observation all-gather: the library's mjb_allgather_obs on its own RCCL communicator (auto: when the backend is nccl) or torch.distributed")
     ap.add_argument("--all-ranks-device0", action="store_true", help="rehearsal on a one-GPU box: every rank uses cuda:0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (the gathered observation ring of the "
+                         "last launch, the state after the last step) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.chunk < 1 or args.obs_every < 1:
         raise SystemExit("bench.py: --steps / --chunk / --obs-every must be >= 1 and --warmup >= 0")
@@ -183,6 +216,8 @@ def main() -> None:
     nq, nv, nu = env.model.nq, env.model.nv, env.model.nu
     chunk = max(1, min(args.chunk, args.steps))               # steps fused per launch
     nlaunch = (args.steps + chunk - 1) // chunk
+    if args.dump_outputs and 4 * (chunk // min(args.obs_every, chunk) * obs_dim + nq + 2 * nv + nu) > DUMP_BUDGET_BYTES:
+        raise SystemExit("bench.py: --dump-outputs: one environment's observation ring and state exceed the 64 MB of the dump: lower --chunk or raise --obs-every")
     pool = _event_pool(torch, max(nlaunch, 6) + 6)
 
     def run(e, nsteps: int) -> None:
@@ -193,10 +228,12 @@ def main() -> None:
             e.rollout(n, obs_every=min(args.obs_every, n), gather=True)
             done += n
 
-    # the same with the kernel bracketed by a pair of HIP events (pre-created); the gather is issued right behind the closing event
-    def run_timed(e, nsteps: int, events: list, per_launch: int | None = None) -> None:
+    # the same with the kernel bracketed by a pair of HIP events (pre-created); the gather is issued right behind the closing event.
+    # Returns the gathered observation ring of the last launch (what a caller of the path receives).
+    def run_timed(e, nsteps: int, events: list, per_launch: int | None = None):
         done = 0
         c = per_launch or chunk
+        gathered = None
         while done < nsteps:
             n = min(c, nsteps - done)
             e0, e1 = pool[len(events)]
@@ -204,8 +241,9 @@ def main() -> None:
             obs = e.rollout(n, obs_every=min(args.obs_every, n))
             e1.record()
             events.append((e0, e1, n))
-            e.gather_observations(obs)
+            gathered = e.gather_observations(obs)
             done += n
+        return gathered
 
     def barrier() -> None:
         if distributed:
@@ -219,7 +257,7 @@ def main() -> None:
     barrier()
     events: list = []
     t0 = time.perf_counter()
-    run_timed(env, args.steps, events)
+    last_obs = run_timed(env, args.steps, events)
     barrier()
     elapsed = time.perf_counter() - t0
     if distributed:
@@ -227,6 +265,15 @@ def main() -> None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     flags = sim.engine_flags()                                  # waits for the stream; bit 3 (hand-over timed out) has already raised in barrier()
+    dumped = None
+    if args.dump_outputs:
+        # taken before anything else runs on this environment: the observation ring of the last timed launch and the state after the
+        # last timed step, all-gathered over the ranks like the ring (every rank takes part; rank 0 writes)
+        outputs = {"obs": last_obs, **{name: env.gather_observations(sim.torch_view(name)) for name in DUMP_STATE}}
+        outputs = {k: v.cpu().numpy() for k, v in outputs.items()}
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, outputs, global_batch)
+        del outputs
 
     # companion figure for N > 1 (all ranks take part): the SAME per-GPU work as the N = 1 run (per-GPU batch = the global batch of
     # BASELINE's config), i.e. the weak-scaling point next to the strong-scaling headline.  Never `value`.
@@ -353,6 +400,8 @@ def main() -> None:
                                      "note": "one wave alone issues a VALU instruction every 4 cycles, so two resident waves per SIMD can reach 1.0 only with no waits at all"}
         if weak_companion is not None:
             out["weak_scaling_companion"] = weak_companion
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if ws == 1 and not args.no_other_configs:
             # continuity with rounds 1-2 (ten 100-step launches, an all-gather each): same workload, the older launch shape
             pool.extend(_event_pool(torch, 4))

@@ -888,3 +888,29 @@ def test_drone_example_law_with_yaw_shaping_and_integral_matches_its_literal_res
     # without integrators the same controller class is the fused device law again
     plain = mt.LinearFeedbackController(K=Kf, ctrl0=u_hover, qpos_goal=q_goal)
     assert make(plain, 2).can_fuse()
+
+
+def test_bench_dump_outputs_hold_what_the_timed_path_computed_in_its_last_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the observation ring of the last timed launch and the state after the last timed step: bit
+    for bit what the same rollout (5 warm-up steps, then the 30 timed ones in one launch) returns in this process."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5", "--global-batch", "64",
+                        "--obs-every", "10", "--no-cpu-baseline", "--no-host-loop", "--no-other-configs", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 30 and line["ms_per_step"] > 0 and not line["outputs_dumped"]["sampled"]
+    got = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in ("obs", "qpos", "qvel", "ctrl", "qacc")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    env = mt.Env.from_xml_path(MODELS["humanoid"], obs_spec=mt.ObservationSpec(as_dict=False), controller=mt.RandomCtrlController(seed=0, scale=1.0),
+                               batch=64, shard=True, dtype="float32")
+    env.rollout(5, obs_every=5)
+    ring = env.rollout(30, obs_every=10).cpu().numpy()
+    assert got["obs"].shape == (3, 64, env.model.nq + env.model.nv) and np.array_equal(got["obs"], ring)
+    for k in ("qpos", "qvel", "ctrl", "qacc"):
+        assert np.array_equal(got[k], env.data.sim.torch_view(k).cpu().numpy()), k
+    np.testing.assert_allclose(got["obs"][-1], np.concatenate([got["qpos"], got["qvel"]], axis=1), rtol=1e-6, atol=1e-6)   # the ring's last row: the last step

@@ -269,6 +269,34 @@ def test_bench_wrong_world_size_is_refused():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
 
 
+def test_bench_dump_outputs_whole_then_seeded_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: arrays that fit are written whole; beyond the budget every array keeps the SAME environments, a
+    fixed seeded sample whose indices are written beside them, so two runs with the same arguments write the same elements."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B = 1000
+    rng = np.random.default_rng(5)
+    outputs = {"obs": rng.standard_normal((3, B, 7)).astype(np.float32), "qpos": rng.standard_normal((B, 5)).astype(np.float32)}
+    info = bench.dump_outputs(str(tmp_path / "whole"), outputs, B)
+    assert not info["sampled"] and sorted(os.listdir(tmp_path / "whole")) == ["obs.npy", "qpos.npy"]
+    for k, a in outputs.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    budget = 40 * (3 * 7 + 5) * 4                                                   # room for 40 environments
+    runs = [bench.dump_outputs(str(tmp_path / f"s{k}"), outputs, B, budget=budget) for k in range(2)]
+    assert runs[0] == {**runs[1], "dir": runs[0]["dir"]} and runs[0]["sampled"] and runs[0]["environments"] == 40
+    idx = np.load(tmp_path / "s0" / "sample_env_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "s1" / "sample_env_index.npy"))
+    assert np.all(np.diff(idx) > 0)
+    idx = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s0" / "obs.npy"), outputs["obs"][:, idx])
+    assert np.array_equal(np.load(tmp_path / "s0" / "qpos.npy"), outputs["qpos"][idx])
+    assert sum(a.nbytes for a in outputs.values()) * 40 // B <= budget
+
+
 def test_batched_manifold_helpers_through_the_c_abi_match_oracle(oracle):
     """mjb_integrate_pos / mjb_differentiate_pos: float64, [batch, nq] <-> [batch, nv], against the oracle's
     mjo_integrate_pos / mjo_differentiate_pos (reference call sites linearization.py:12,67,77; lqr.py:153)."""
