@@ -99,12 +99,17 @@ int mjb_sync(mjbData* d);
  * further launch (mjb_step, mjb_rollout, mjb_forward ...) the library returns MJB_ERR_DEVICE until mjb_reset clears the flags; the
  * environments concerned were NOT advanced (their arrays hold the state the failed launch started from). */
 int mjb_engine_flags(mjbData* d, int* flags_out);
+/* the same word WITHOUT waiting for the stream (device-resident loops: no host synchronisation): what the launches that have finished
+ * so far raised, read from the pinned words the kernels store (reference FatalError / warning surfacing, env.py:186-190) */
+int mjb_engine_flags_peek(mjbData* d, int* flags_out);
 int mjb_data_info(mjbData* d, int* batch, int* dtype, int* lanes, int* nconmax, int* nefcmax, int* lds_bytes_per_env);
 
 /* device pointer of a [batch, n] state array: qpos qvel ctrl qacc qacc_warmstart (dtype of the data),
- * time (float64 [batch]), xpos xquat xipos site_xpos geom_xpos subtree_com sensordata qfrc_inverse actuator_moment, counters (int32 [batch, 8]) */
+ * time (float64 [batch]), xpos xquat xipos site_xpos geom_xpos subtree_com sensordata qfrc_inverse actuator_moment, counters (int32 [batch, 8]),
+ * episode (resets per environment by mjb_reset_envs: uint32 bits, reported as int32 [batch, 1]) */
 int mjb_array_ptr(mjbData* d, const char* name, void** dev_ptr, long* per_env, int* dtype);
-/* host <-> device copies with conversion to/from float64 (state snapshot/restore, reference state_utils.py:9-31) */
+/* host <-> device copies with conversion to/from float64 (state snapshot/restore, reference state_utils.py:9-31); "episode" is
+ * read-only and mjb_get_array widens its uint32 values (counters: mjb_get_counters) */
 int mjb_get_array(mjbData* d, const char* name, double* host_out);
 int mjb_set_array(mjbData* d, const char* name, const double* host_in);
 int mjb_get_counters(mjbData* d, int* host_out /* [batch, 8] */);
@@ -162,6 +167,15 @@ int mjb_fd_spec_unload(mjbData* d);
 int mjb_reset(mjbData* d, int key);
 /* mj_forward (reference model.py:53-54): fills qacc and the kinematic outputs */
 int mjb_forward(mjbData* d);
+/* Per-environment mj_resetData / mj_resetDataKeyframe (reference model.py:59-71) and mj_forward (reference model.py:53-54), both on the
+ * data's stream, the mask read on the device (no host synchronisation).  mask_dev: [batch] bytes in device-accessible memory, non-zero =
+ * this environment; NULL = every environment.  mjb_reset_envs: key < 0 = qpos0; qacc = qacc_warmstart = 0, counters zeroed, time of the
+ * keyframe, array "episode" (uint32 [batch], zeroed at creation) + 1; optional uniform noise (float64, rounded once to the data dtype):
+ * dq = qpos_noise (2u - 1) applied as mj_integratePos(qpos, dq, 1) over the nv dofs, qvel += qvel_noise (2u - 1), u a Philox4x32-10
+ * draw keyed (seed, 0x5EED) with counter (env0 + e, episode[e] before the increment, i, 1 for qpos / 2 for qvel).  Unlike mjb_reset the
+ * sticky engine flags are left alone.  mjb_forward_envs: environments outside the mask keep every array. */
+int mjb_reset_envs(mjbData* d, int key, const unsigned char* mask_dev, unsigned seed, double qpos_noise, double qvel_noise);
+int mjb_forward_envs(mjbData* d, const unsigned char* mask_dev);
 /* mj_inverse (reference setpoints.py:29-31 steady_ctrl0, examples/humanoid/controllers/lqr.py:57-70): inverse dynamics at the
  * current (qpos, qvel, qacc) of every environment -> array "qfrc_inverse" [batch, nv]; the same pass fills
  * "actuator_moment" [batch, nu, nv] (dense form of data.actuator_moment, which setpoints.py:40-47 densifies).  State is not advanced. */

@@ -13,8 +13,9 @@ from __future__ import annotations
 from . import mj
 from ._typing import InfoDict, JacobianDict, JacobiansDict, Observation, ObservationArray, ObservationDict, StateSnapshot
 from .compat import CompatibilityReport, check_controller_compat
-from .control import ControlSpace, Controller, ControllerCapabilities
+from .control import ControlSpace, Controller, ControllerCapabilities, uses_device_arrays
 from .controllers import LinearFeedbackController, PositionTargetDemo, RandomCtrlController, ZeroController
+from .device_data import DeviceData
 from .env import Env, StepResult
 from .exceptions import CompatibilityError, ConfigError, LinearizationError, NameLookupError, TemplateError
 from .jacobians import compute_requested_jacobians
@@ -33,6 +34,6 @@ __all__ = [
     "ObservationProducer", "ModelHandle", "CompatibilityReport", "StepResult", "Env", "ZeroController",
     "PositionTargetDemo", "RandomCtrlController", "LinearFeedbackController", "check_controller_compat", "linearize_discrete",
     "compute_requested_jacobians", "StepHook", "iterate_passive", "run_passive_headless", "steady_ctrl0", "DataProbe",
-    "StateControlRecorder", "TrajectoryLogger", "ObservationDict",
+    "StateControlRecorder", "TrajectoryLogger", "ObservationDict", "DeviceData", "uses_device_arrays",
     "ObservationArray", "Observation", "JacobianDict", "JacobiansDict", "InfoDict", "StateSnapshot", "__version__",
 ]

@@ -69,6 +69,9 @@ def load_library() -> ctypes.CDLL:
     L.mjb_get_counters.argtypes = [vp, vp]
     L.mjb_reset.argtypes = [vp, ci]
     L.mjb_forward.argtypes = [vp]
+    L.mjb_reset_envs.argtypes = [vp, ci, vp, cu, cd, cd]
+    L.mjb_forward_envs.argtypes = [vp, vp]
+    L.mjb_engine_flags_peek.argtypes = [vp, pci]
     L.mjb_model_spec_source.argtypes = [vp, ci, ci, ci, ci, ctypes.c_char_p, cl]
     L.mjb_model_spec_source.restype = cl
     L.mjb_spec_source.argtypes = [vp, ctypes.c_char_p, cl]
@@ -137,7 +140,8 @@ def load_library() -> ctypes.CDLL:
                  "mjb_forward", "mjb_inverse", "mjb_spec_load", "mjb_spec_unload", "mjb_fd_spec_load", "mjb_fd_spec_unload", "mjb_step2_spec_load", "mjb_step2_spec_unload", "mjb_step", "mjb_rollout", "mjb_obs_spec_create", "mjb_obs_dim", "mjb_obs_gather",
                  "mjb_transition_fd", "mjb_jac", "mjb_debug_forward", "mjb_debug_get", "mjb_model_field", "mjb_model_field_at", "mjb_model_save",
                  "mjb_model_load", "mjb_model_load_xml", "mjb_model_load_xml_string", "mjb_integrate_pos", "mjb_differentiate_pos", "mjb_host_view", "mjb_sync_to_host", "mjb_sync_to_device",
-                 "mjb_step_host", "mjb_mirror_edited_mask", "mjb_mirror_commit", "mjb_step_host_auto", "mjb_engine_flags"):
+                 "mjb_step_host", "mjb_mirror_edited_mask", "mjb_mirror_commit", "mjb_step_host_auto", "mjb_engine_flags",
+                 "mjb_reset_envs", "mjb_forward_envs", "mjb_engine_flags_peek"):
         getattr(L, name).restype = ci
     _LIB = L
     return L
@@ -530,7 +534,9 @@ class BatchSim:
     def use_torch_stream(self) -> None:
         import torch
 
-        self.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = torch.cuda.current_stream(self.device)
+        self.set_stream(stream.cuda_stream)
+        self._torch_stream = stream                                 # the library's stream handle stays valid while it is bound
 
     def sync(self) -> None:
         _check(load_library().mjb_sync(self.ptr))
@@ -602,6 +608,12 @@ class BatchSim:
         """upload the edited mirror fields, ``nstep`` x mj_step (0: mj_forward), refresh the mirror — one library call."""
         _check(load_library().mjb_step_host(self.ptr, int(nstep), int(field_mask)))
 
+    def engine_flags_peek(self) -> int:
+        """The same word WITHOUT waiting for the stream (``mjb_engine_flags_peek``): what the launches that have finished so far raised."""
+        out = ctypes.c_int(0)
+        _check(load_library().mjb_engine_flags_peek(self.ptr, ctypes.byref(out)))
+        return int(out.value)
+
     def engine_flags(self) -> int:
         """Sticky flag word of the batch after waiting for the stream (``mjb_engine_flags``): bit 0 contacts dropped, 1 constraint rows
         dropped, 2 bad-state auto-reset, 3 a ticket-mode launch timed out on a hand-over (the one that makes every synchronising call
@@ -621,6 +633,52 @@ class BatchSim:
 
     def forward(self) -> None:
         _check(load_library().mjb_forward(self.ptr))
+
+    # -- per-environment reset / forward (mjb_reset_envs / mjb_forward_envs): the mask is read on the device ------------------------
+    def env_mask(self, mask):
+        """``mask`` as a [batch] one-byte torch tensor on this object's GPU (``None`` stays ``None`` = every environment).  A torch bool /
+        uint8 tensor on that device is used as it is (zero-copy); an index sequence or a numpy bool array is uploaded once."""
+        import torch
+
+        if mask is None:
+            return None
+        dev = torch.device(f"cuda:{self.device}")
+        if isinstance(mask, torch.Tensor):
+            if mask.dtype not in (torch.bool, torch.uint8):
+                raise ConfigError(f"environment mask must be a bool or uint8 tensor, got {mask.dtype}")
+            if tuple(mask.shape) != (self.batch,):
+                raise ConfigError(f"environment mask must have shape [{self.batch}], got {list(mask.shape)}")
+            if mask.device != dev:
+                raise ConfigError(f"environment mask must live on {dev}, got {mask.device}")
+            return mask if mask.is_contiguous() else mask.contiguous()
+        arr = np.asarray(mask)
+        if arr.dtype == np.bool_:
+            if arr.shape != (self.batch,):
+                raise ConfigError(f"environment mask must have shape [{self.batch}], got {list(arr.shape)}")
+            host = arr.astype(np.uint8)
+        else:
+            if arr.ndim != 1 or (arr.size and not np.issubdtype(arr.dtype, np.integer)):
+                raise ConfigError("environment mask must be a bool mask [batch] or a sequence of environment indices")
+            idx = arr.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= self.batch):
+                raise ConfigError(f"environment index out of range [0, {self.batch})")
+            host = np.zeros(self.batch, dtype=np.uint8)
+            host[idx] = 1
+        return torch.from_numpy(host).to(dev)
+
+    def reset_envs(self, mask=None, key: int = -1, seed: int = 0, qpos_noise: float = 0.0, qvel_noise: float = 0.0) -> None:
+        """mj_resetData / mj_resetDataKeyframe (key < 0: qpos0) of the masked environments only, with optional uniform reset noise
+        (``mjb_reset_envs``); the sticky engine flags are left alone.  Runs on the data's stream, no host synchronisation."""
+        m = self.env_mask(mask)
+        self._mask_keep = m                                         # alive at least until the next masked call on this object
+        _check(load_library().mjb_reset_envs(self.ptr, int(key), ctypes.c_void_p(m.data_ptr()) if m is not None else None,
+                                             int(seed) & 0xFFFFFFFF, float(qpos_noise), float(qvel_noise)))
+
+    def forward_envs(self, mask=None) -> None:
+        """mj_forward of the masked environments only (``mjb_forward_envs``): the others keep every array."""
+        m = self.env_mask(mask)
+        self._mask_keep_fwd = m
+        _check(load_library().mjb_forward_envs(self.ptr, ctypes.c_void_p(m.data_ptr()) if m is not None else None))
 
     def inverse(self) -> None:
         """mj_inverse on every environment: fills the arrays ``qfrc_inverse`` [B, nv] and ``actuator_moment`` [B, nu*nv]."""

@@ -9,6 +9,11 @@ Batched addition: a controller whose law can be evaluated inside the fused step 
 ``device_ctrl_mode`` attribute (one of :data:`DEVICE_CTRL_MODES`); ``Env.rollout`` / ``run_passive_headless`` then
 keep the whole loop on the GPU.  :func:`device_ctrl_mode_of` is the single place that decides whether a controller
 qualifies.
+
+Device-resident controllers: a controller with ``device_arrays = True`` keeps the reference's ``prepare`` / ``__call__(model, data,
+t)`` shape, but ``data`` is a :class:`~mujoco_template_amd.device_data.DeviceData` (zero-copy torch views of the GPU state) and ``t``
+its ``time`` tensor ``[batch]``; it writes ``data.ctrl`` in place on the device (a torch policy, MPC sampling, ...).
+:func:`uses_device_arrays` is the single place that decides whether a controller is one.
 """
 
 from __future__ import annotations
@@ -62,4 +67,20 @@ def device_ctrl_mode_of(controller: Any) -> str | None:
     return mode
 
 
-__all__ = ["ControlSpace", "ControllerCapabilities", "Controller", "DEVICE_CTRL_MODES", "device_ctrl_mode_of"]
+def uses_device_arrays(controller: Any) -> bool:
+    """True when ``controller`` is called with device arrays (``device_arrays = True``).
+
+    Raises :class:`~mujoco_template_amd.exceptions.ConfigError` when it also asks for the linearisation or Jacobians: those are
+    evaluated on the host mirror, which the device-resident loop never refreshes.
+    """
+    if controller is None or getattr(controller, "device_arrays", False) is not True:
+        return False
+    caps = getattr(controller, "capabilities", None)
+    if caps is not None and (caps.needs_linearization or tuple(caps.needs_jacobians)):
+        from .exceptions import ConfigError
+
+        raise ConfigError("a controller with device_arrays=True cannot use needs_linearization / needs_jacobians (host-side quantities)")
+    return True
+
+
+__all__ = ["ControlSpace", "ControllerCapabilities", "Controller", "DEVICE_CTRL_MODES", "device_ctrl_mode_of", "uses_device_arrays"]

@@ -47,7 +47,7 @@ struct DevAlloc {
   void release() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
 };
 
-struct ArrayInfo { void* ptr; long per_env; int kind; };  // kind: 0 = data dtype, 1 = float64, 2 = int32
+struct ArrayInfo { void* ptr; long per_env; int kind; };  // kind: 0 = data dtype, 1 = float64, 2 = int32, 3 = uint32 (int32 to mjb_array_ptr, widened by mjb_get_array)
 }  // namespace
 
 struct mjbModel {
@@ -128,6 +128,7 @@ struct mjbData {
   unsigned long long mirror_seq = 0;      // sequence number of the last polled host-driven step (completion words behind the flags word)
   size_t mirror_off[7] = {0, 0, 0, 0, 0, 0, 0};             // element offsets of the six fields, [6] = total
   int* flags_pin = nullptr;               // pinned: the four engine-flag bits as words the kernels set (DevData::flags_pin)
+  unsigned* episode = nullptr;            // [batch] resets per environment by mjb_reset_envs (the episode counter of its noise streams)
   unsigned xfer_timeout = 0;              // ticks of the 100 MHz clock a wave waits for a hand-over (0 = not yet read from MJB_XFER_TIMEOUT_MS)
   int xfer_poison_env = -1;               // test hook MJB_XFER_POISON_ENV (-1 = not yet read)
 };
@@ -231,6 +232,8 @@ template <typename TS> int alloc_state(mjbData* d, DevData<TS>& s) {
   A["subtree_com"] = {s.subtree_com, h.nbody * 3L, 0}; A["sensordata"] = {s.sensordata, h.nsensordata, 0};
   A["qfrc_inverse"] = {s.qfrc_inverse, h.nv, 0}; A["actuator_moment"] = {s.actuator_moment, (long)h.nu * h.nv, 0};
   A["counters"] = {s.counters, CNT_N, 2};
+  if (dev_alloc(d, &d->episode, B)) return -1;
+  A["episode"] = {d->episode, 1, 3};
   return 0;
 }
 
@@ -611,14 +614,15 @@ int copy_out(mjbData* d, const ArrayInfo& ai, double* host_out) {
   size_t n = (size_t)d->batch * ai.per_env;
   if (n == 0) return MJB_OK;
   const bool wide = ai.kind == 1 || (ai.kind == 0 && d->dtype == MJB_F64);
-  if (!wide && ai.kind != 0) return fail(MJB_ERR_ARG, "integer array requested as float64");
+  if (!wide && ai.kind != 0 && ai.kind != 3) return fail(MJB_ERR_ARG, "integer array requested as float64");
   const size_t bytes = n * (wide ? sizeof(double) : sizeof(float));
   int rc = ensure_io_pin(d, bytes);
   if (rc != MJB_OK) return rc;
   HIPCHK(hipMemcpyAsync(d->io_pin, ai.ptr, bytes, hipMemcpyDeviceToHost, d->stream));   // ordered behind whatever the stream still runs
   HIPCHK(hipStreamSynchronize(d->stream));
   { int ec = engine_check(d); if (ec != MJB_OK) return ec; }
-  if (wide) std::memcpy(host_out, d->io_pin, bytes);
+  if (ai.kind == 3) { const unsigned* src = (const unsigned*)d->io_pin; for (size_t i = 0; i < n; i++) host_out[i] = (double)src[i]; }
+  else if (wide) std::memcpy(host_out, d->io_pin, bytes);
   else { const float* src = (const float*)d->io_pin; for (size_t i = 0; i < n; i++) host_out[i] = (double)src[i]; }
   return MJB_OK;
 }
@@ -745,6 +749,14 @@ int mjb_engine_flags(mjbData* d, int* flags_out) {
   return MJB_OK;
 }
 
+int mjb_engine_flags_peek(mjbData* d, int* flags_out) {
+  if (!d || !flags_out) return fail(MJB_ERR_ARG, "NULL argument");
+  int fl = 0;
+  for (int k = 0; k < 4; k++) if (d->flags_pin && __atomic_load_n(d->flags_pin + k, __ATOMIC_ACQUIRE) != 0) fl |= 1 << k;
+  *flags_out = fl;
+  return MJB_OK;
+}
+
 int mjb_data_info(mjbData* d, int* batch, int* dtype, int* lanes, int* nconmax, int* nefcmax, int* lds_bytes_per_env) {
   if (!d) return fail(MJB_ERR_ARG, "data is NULL");
   if (batch) *batch = d->batch;
@@ -762,7 +774,7 @@ int mjb_array_ptr(mjbData* d, const char* name, void** dev_ptr, long* per_env, i
   if (it == d->arrays.end()) return fail(MJB_ERR_ARG, std::string("unknown array: ") + name);
   if (dev_ptr) *dev_ptr = it->second.ptr;
   if (per_env) *per_env = it->second.per_env;
-  if (dtype) *dtype = it->second.kind == 0 ? d->dtype : (it->second.kind == 1 ? MJB_F64 : 2);
+  if (dtype) *dtype = it->second.kind == 0 ? d->dtype : (it->second.kind == 1 ? MJB_F64 : 2);      // (uint32 "episode": int32 bits)
   return MJB_OK;
 }
 
@@ -783,7 +795,7 @@ int mjb_set_array(mjbData* d, const char* name, const double* host_in) {
   if (n == 0) return MJB_OK;
   HIPCHK(hipSetDevice(d->device));
   const bool wide = ai.kind == 1 || (ai.kind == 0 && d->dtype == MJB_F64);
-  if (!wide && ai.kind != 0) return fail(MJB_ERR_ARG, "integer arrays are read-only");
+  if (!wide && ai.kind != 0) return fail(MJB_ERR_ARG, "integer arrays are read-only");   // (counters, episode)
   const size_t bytes = n * (wide ? sizeof(double) : sizeof(float));
   int rc = ensure_io_pin(d, bytes);
   if (rc != MJB_OK) return rc;
@@ -824,6 +836,28 @@ int mjb_reset(mjbData* d, int key) {
   // a reset also clears the sticky engine flags (k_reset, in stream order); after a failed ticket launch the host-visible word must be
   // clear before the next launch's entry check reads it: wait for the reset in that (rare) case
   if (d->flags_pin && __atomic_load_n(d->flags_pin + 3, __ATOMIC_ACQUIRE) != 0) HIPCHK(hipStreamSynchronize(d->stream));
+  return MJB_OK;
+}
+
+int mjb_reset_envs(mjbData* d, int key, const unsigned char* mask_dev, unsigned seed, double qpos_noise, double qvel_noise) {
+  if (!d) return fail(MJB_ERR_ARG, "data is NULL");
+  const HostModel& h = d->model->h;
+  if (key >= h.nkey) return fail(MJB_ERR_LOOKUP, "keyframe index out of range");
+  if (!(qpos_noise >= 0) || !(qvel_noise >= 0) || std::isinf(qpos_noise) || std::isinf(qvel_noise)) return fail(MJB_ERR_ARG, "reset noise must be finite and >= 0");
+  HIPCHK(hipSetDevice(d->device));
+  // float64 tables whatever the data dtype: the noise is computed in float64 and rounded once (without noise: the fp32 tables' values)
+  ResetSpec r;
+  r.nq = h.nq; r.nv = h.nv; r.nu = h.nu; r.njnt = h.njnt;
+  r.jnt_type = d->md.jnt_type; r.jnt_qposadr = d->md.jnt_qposadr; r.jnt_dofadr = d->md.jnt_dofadr;
+  r.qpos = key >= 0 ? d->md.key_qpos + (size_t)key * h.nq : d->md.qpos0;
+  r.qvel = key >= 0 ? d->md.key_qvel + (size_t)key * h.nv : nullptr;
+  r.ctrl = key >= 0 ? d->md.key_ctrl + (size_t)key * h.nu : nullptr;
+  r.time = key >= 0 ? h.D("key_time")[key] : 0.0;
+  r.seed = seed; r.qpos_noise = qpos_noise; r.qvel_noise = qvel_noise;
+  const int threads = 64, grid = (d->batch + threads - 1) / threads;
+  if (d->dtype == MJB_F32) hipLaunchKernelGGL(k_reset_envs<float>, dim3(grid), dim3(threads), 0, d->stream, d->df, r, mask_dev, (unsigned)d->env0, d->episode);
+  else hipLaunchKernelGGL(k_reset_envs<double>, dim3(grid), dim3(threads), 0, d->stream, d->dd, r, mask_dev, (unsigned)d->env0, d->episode);
+  HIPCHK(hipGetLastError());
   return MJB_OK;
 }
 
@@ -968,6 +1002,15 @@ int mjb_forward(mjbData* d) {
   HIPCHK(hipSetDevice(d->device));
   ObsSpecDev none; std::memset(&none, 0, sizeof(none));
   return launch(d, make_args(d, 1, MJB_CTRL_KEEP, 0, 0, 1.0, 1), none, nullptr, false);
+}
+
+int mjb_forward_envs(mjbData* d, const unsigned char* mask_dev) {
+  if (!d) return fail(MJB_ERR_ARG, "data is NULL");
+  HIPCHK(hipSetDevice(d->device));
+  ObsSpecDev none; std::memset(&none, 0, sizeof(none));
+  StepArgs a = make_args(d, 1, MJB_CTRL_KEEP, 0, 0, 1.0, 1);
+  a.env_mask = mask_dev;
+  return launch(d, a, none, nullptr, false);
 }
 
 int mjb_inverse(mjbData* d) {

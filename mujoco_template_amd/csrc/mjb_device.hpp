@@ -2881,6 +2881,59 @@ template <typename T, int G> MJB_DEV void reset_state(Ctx<T>& c) {
   gsync<G>();
 }
 
+// What k_reset_envs resets an environment to (mjb_reset_envs): the float64 model tables, plain pointers.
+struct ResetSpec {
+  int nq, nv, nu, njnt;
+  const int *jnt_type, *jnt_qposadr, *jnt_dofadr;
+  const double *qpos, *qvel, *ctrl;    // base state: qpos0 or keyframe `key`; qvel / ctrl null = 0
+  double time;
+  unsigned seed;
+  double qpos_noise, qvel_noise;
+};
+// Uniform draw in [0, 1) of the reset noise: philox_first keyed (seed, 0x5EED), counter (global env, episode, i, stream) with
+// stream 1 = qpos (tangent space), 2 = qvel.  random_ctrl's counters have c3 = 0: the streams never share a counter.
+MJB_DEV double reset_uniform(unsigned seed, unsigned genv, unsigned episode, unsigned i, unsigned stream) {
+  return (double)(philox_first(genv, episode, i, stream, seed, 0x5EEDu) >> 8) * (1.0 / 16777216.0);
+}
+// mj_resetData / mj_resetDataKeyframe of ONE environment (the per-environment body of k_reset_envs), with optional noise:
+//   dq_i   = qpos_noise (2u - 1) over the nv dofs, qpos = mj_integratePos(base, dq, 1): free / ball quaternions are rotated and stay unit
+//   qvel_i = base_i + qvel_noise (2u - 1)
+// in float64 (the arithmetic of mjb_integrate_pos), rounded once to TS; qacc = qacc_warmstart = 0.  Counters, time and the episode
+// number are the caller's; the sticky engine flags are NOT touched (a partial reset must not hide another environment's failure).
+template <typename TS>
+MJB_DEV void reset_env_state(const ResetSpec& r, unsigned genv, unsigned episode, TS* qpos, TS* qvel, TS* ctrl, TS* qacc, TS* qacc_ws) {
+  for (int i = 0; i < r.nq; i++) qpos[i] = (TS)r.qpos[i];
+  if (r.qpos_noise != 0) {
+    for (int j = 0; j < r.njnt; j++) {
+      const int qa = r.jnt_qposadr[j], da = r.jnt_dofadr[j], t = r.jnt_type[j];
+      double dq[6];
+      const int nd = t == JNT_FREE ? 6 : (t == JNT_BALL ? 3 : 1);
+      for (int k = 0; k < nd; k++) dq[k] = r.qpos_noise * (2.0 * reset_uniform(r.seed, genv, episode, (unsigned)(da + k), 1u) - 1.0);
+      if (t == JNT_HINGE || t == JNT_SLIDE) { qpos[qa] = (TS)(r.qpos[qa] + dq[0]); continue; }
+      int qr = qa;
+      const double* w = dq;
+      if (t == JNT_FREE) {
+        for (int k = 0; k < 3; k++) qpos[qa + k] = (TS)(r.qpos[qa + k] + dq[k]);
+        qr = qa + 3; w = dq + 3;
+      }
+      const double nrm = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+      if (nrm < 1e-15) continue;
+      const double sn = sin(0.5 * nrm) / nrm;
+      const double rot[4] = {cos(0.5 * nrm), w[0] * sn, w[1] * sn, w[2] * sn}, q0[4] = {r.qpos[qr], r.qpos[qr + 1], r.qpos[qr + 2], r.qpos[qr + 3]};
+      double out[4];
+      quat_mul(out, q0, rot);
+      const double on = sqrt(out[0] * out[0] + out[1] * out[1] + out[2] * out[2] + out[3] * out[3]);
+      for (int k = 0; k < 4; k++) qpos[qr + k] = on < 1e-15 ? (TS)(k == 0 ? 1 : 0) : (TS)(out[k] / on);
+    }
+  }
+  for (int i = 0; i < r.nv; i++) {
+    double v = r.qvel ? r.qvel[i] : 0.0;
+    if (r.qvel_noise != 0) v += r.qvel_noise * (2.0 * reset_uniform(r.seed, genv, episode, (unsigned)i, 2u) - 1.0);
+    qvel[i] = (TS)v; qacc[i] = 0; qacc_ws[i] = 0;
+  }
+  for (int i = 0; i < r.nu; i++) ctrl[i] = r.ctrl ? (TS)r.ctrl[i] : (TS)0;
+}
+
 // flat observation (keys in sorted order, reference observations.py:171-174):
 // bodies_pos, ctrl, geoms_pos, qpos, qvel, sensordata, sites_pos, subtree_com, time
 template <typename T, typename TS, int G> MJB_DEV void write_obs(const Ctx<T>& c, ObsRef s, double time, TS* out) {

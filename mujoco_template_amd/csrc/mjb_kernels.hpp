@@ -38,6 +38,12 @@ MJB_DEV void k_step_body() {
 #else
 #define MJB_TLACC nullptr
 #endif
+  // masked forward (mjb_forward_envs; never the ticket map): a group whose environment's mask byte is 0 leaves before the loop and keeps
+  // every array.  Here, in front of the loop, the check leaves the loop's register allocation as it was (inside it: +12 VGPR spills).
+  if (kp->a.mode == 1 && kp->a.env_mask) {
+    const int env = (int)blockIdx.x * (64 / G) + (int)(threadIdx.x / G);
+    if (env < kp->d.batch && !kp->a.env_mask[env]) return;
+  }
   // ONE call site of env_run (the forward pipeline is inlined once): the static map is the loop below with a single pass
   for (;;) {
     asm volatile("" : "+s"(kp));
@@ -340,6 +346,20 @@ __global__ void k_reset(DevData<TS> d, int nq, int nv, int nu, const TS* qpos, c
   for (int i = 0; i < nu; i++) d.ctrl[tid * nu + i] = ctrl ? ctrl[i] : (TS)0;
   d.time[tid] = time;
   for (int i = 0; i < CNT_N; i++) d.counters[tid * CNT_N + i] = 0;
+}
+
+// Per-environment reset (mjb_reset_envs): one thread per environment; only those whose mask byte is non-zero (mask null: all).  State
+// from reset_env_state (mjb_device.hpp), time of the keyframe, counters zeroed, episode number + 1.  Unlike k_reset it leaves the
+// sticky engine flags alone.
+template <typename TS>
+__global__ void k_reset_envs(DevData<TS> d, ResetSpec r, const unsigned char* mask, unsigned env0, unsigned* episode) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= d.batch || (mask && !mask[e])) return;
+  const unsigned ep = episode[e];
+  reset_env_state<TS>(r, env0 + (unsigned)e, ep, d.qpos + e * r.nq, d.qvel + e * r.nv, d.ctrl + e * r.nu, d.qacc + e * r.nv, d.qacc_warmstart + e * r.nv);
+  d.time[e] = r.time;
+  for (int i = 0; i < CNT_N; i++) d.counters[e * CNT_N + i] = 0;
+  episode[e] = ep + 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

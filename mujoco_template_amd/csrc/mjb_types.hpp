@@ -168,6 +168,7 @@ struct StepArgs {
   int nuniform, nchunk;  // ticket mode, the chunk plan of an environment's nstep steps: `nuniform` chunks of chunk_steps steps, then every
                          // further chunk takes HALF of what is left (guided taper down to single steps: the launch's tail is half of the
                          // LAST chunk); nchunk = all chunks.  chunk_plan() below is the one definition, used by host and device.
+  const unsigned char* env_mask;   // forward mode (mjb_forward_envs): [batch] bytes, 0 = leave that environment alone; nullptr = all
 };
 
 // Chunk k of the plan (nstep, chunk_steps, nuniform): steps [s0, s1).  Host and device.

@@ -17,7 +17,11 @@ What the batched engine adds:
 * two ways through a step.  *Host-driven*: any Python controller, one engine call per sub-step (``_advance_on_host``).
   *Fused*: a controller whose law the step kernel can evaluate itself (``control.device_ctrl_mode_of``) runs inside ONE
   kernel launch for all sub-steps (``rollout``); ``step`` picks it automatically;
-* :meth:`Env.rollout` - the fused path exposed directly, optionally filling a device-side observation ring.
+* :meth:`Env.rollout` - the fused path exposed directly, optionally filling a device-side observation ring;
+* a third way through a step for controllers written in torch (``device_arrays = True``, ``control.uses_device_arrays``): the
+  controller reads and writes the GPU state through :class:`~mujoco_template_amd.device_data.DeviceData`, the engine steps it in
+  place, the observation is gathered on the device - no host mirror anywhere in the loop (``_step_device``);
+* per-environment resets: ``reset(envs=...)`` and ``reset_done=True`` (done environments restart inside ``step``, on the device).
 """
 
 from __future__ import annotations
@@ -32,7 +36,7 @@ import numpy as np
 from ._capi import CTRL_FEEDBACK, CTRL_KEEP, CTRL_RANDOM, CTRL_ZERO
 from ._typing import InfoDict, JacobiansDict, Observation
 from .compat import check_controller_compat
-from .control import Controller, device_ctrl_mode_of
+from .control import Controller, device_ctrl_mode_of, uses_device_arrays
 from .exceptions import ConfigError, TemplateError
 from .jacobians import compute_requested_jacobians
 from .linearization import linearize_discrete
@@ -45,8 +49,8 @@ _KERNEL_MODE = {"zero": CTRL_ZERO, "random": CTRL_RANDOM, "feedback": CTRL_FEEDB
 @dataclass
 class StepResult:
     obs: Observation | None
-    reward: float | None
-    done: bool
+    reward: float | None          # device-array controllers: a tensor [batch] (or None)
+    done: bool                    # device-array controllers: a bool tensor [batch]
     info: InfoDict
 
 
@@ -60,9 +64,20 @@ class Env:
                  reward_fn: Callable[[Any, Any, Observation | None], float] | None = None,
                  done_fn: Callable[[Any, Any, Observation | None], bool] | None = None,
                  info_fn: Callable[[Any, Any, Observation | None], dict] | None = None,
-                 enabled_groups: Iterable[int] | None = None, control_decimation: int = 1):
+                 enabled_groups: Iterable[int] | None = None, control_decimation: int = 1, *, reset_done: bool = False,
+                 reset_noise: tuple[float, float] = (0.0, 0.0), reset_seed: int = 0):
         if control_decimation < 1:
             raise ConfigError("control_decimation must be >= 1")
+        self._device_arrays = uses_device_arrays(controller)        # ConfigError for device arrays + linearisation / Jacobians
+        if reset_done and not (self._device_arrays and done_fn is not None):
+            raise ConfigError("reset_done=True needs a controller with device_arrays=True and a done_fn")
+        qn, qv = (float(x) for x in reset_noise)
+        if not (qn >= 0 and qv >= 0):
+            raise ConfigError("reset_noise must be (qpos_noise >= 0, qvel_noise >= 0)")
+        self.reset_done, self._reset_noise, self._reset_seed = bool(reset_done), (qn, qv), int(reset_seed)
+        self._reset_key = -1              # keyframe of the last whole-batch reset: what reset_done restarts from
+        self._engine_flags_seen = 0       # engine-flag bits the device-resident loop has already reported
+        self._device_data = None
         self.handle, self.model, self.data = handle, handle.model, handle.data
         self.controller = controller
         self.reward_fn, self.done_fn, self.info_fn = reward_fn, done_fn, info_fn
@@ -80,7 +95,7 @@ class Env:
         self.gather_collective = None     # which collective the last gather used (reported by bench.py)
         self._select_actuator_groups(enabled_groups)
         if controller is not None:
-            controller.prepare(self.model, self.data)
+            controller.prepare(self.model, self.device_data if self._device_arrays else self.data)
             report = check_controller_compat(self.model, controller.capabilities, self.handle.enabled_actuator_mask())
             self._compat_warnings = list(report.warnings)     # the report's list replaces the group notes (reference env.py:92)
             report.assert_ok()
@@ -111,7 +126,8 @@ class Env:
                       control_decimation: int = 1, auto_reset: bool = True, keyframe: int | str | None = None,
                       batch: int = 1, dtype: str = "float32", device: int | None = None, lanes: int = 0, nconmax: int = 0,
                       nefcmax: int = 0, env0: int = 0, specialize: bool | None = None, shard: bool = False,
-                      collective: str = "auto") -> "Env":
+                      collective: str = "auto", reset_done: bool = False, reset_noise: tuple[float, float] = (0.0, 0.0),
+                      reset_seed: int = 0) -> "Env":
         """Reference signature (``mujoco_template/env.py:100-143``) + the engine's keywords.  ``shard=True``: ``batch`` is the GLOBAL batch
         of a one-process-per-GPU job (RANK / WORLD_SIZE / LOCAL_RANK from the torchrun environment); this process creates its
         contiguous block on ``cuda:LOCAL_RANK`` (``device`` overrides) with ``env0`` = the block's first global index.
@@ -138,7 +154,8 @@ class Env:
             controller.env0 = env0                  # device-side RNG streams are keyed by the GLOBAL environment index
         env = cls(handle, obs_spec=obs_spec if obs_spec is not None else ObservationSpec(include_sensordata=False),
                   controller=controller, reward_fn=reward_fn, done_fn=done_fn, info_fn=info_fn,
-                  enabled_groups=enabled_groups, control_decimation=control_decimation)
+                  enabled_groups=enabled_groups, control_decimation=control_decimation, reset_done=reset_done,
+                  reset_noise=reset_noise, reset_seed=reset_seed)
         env.shard, env._collective = plan, collective
         if auto_reset:
             env.reset(keyframe)
@@ -150,24 +167,53 @@ class Env:
             self.extractor = ObservationExtractor(self.model, self._obs_spec)
         return self.extractor
 
-    def reset(self, keyframe: int | str | None = None) -> Observation:
+    @property
+    def device_data(self):
+        """Zero-copy torch views of this environment's GPU state (``DeviceData``, built once)."""
+        if self._device_data is None:
+            from .device_data import DeviceData
+
+            self._device_data = DeviceData(self.data)
+        return self._device_data
+
+    def reset(self, keyframe: int | str | None = None, *, envs=None, noise: tuple[float, float] | None = None,
+              seed: int | None = None) -> Observation:
+        """Whole batch (``envs=None``): the reference's reset.  ``envs`` (torch bool / uint8 mask [batch] on the GPU, index sequence or
+        numpy bool mask): reset (``ModelHandle.reset_envs``, optional ``noise = (qpos, qvel)`` amplitudes, default the ``reset_noise`` /
+        ``reset_seed`` of the environment) and forward ONLY those environments, on the device; returns ``observe_device()``."""
+        if envs is not None:
+            return self._reset_envs(envs, keyframe, noise, seed)
+        if noise is not None or seed is not None:
+            raise ConfigError("reset(noise=, seed=) applies to a per-environment reset: pass envs=")
         if keyframe is None:
             self.handle.reset()
         else:
             self.handle.reset_keyframe(keyframe)
+        self._reset_key = -1 if keyframe is None else self.handle._keyframe_index(keyframe)
         self.handle.forward()
         self._substep = self._device_steps = 0
         self._warnings_reported = False
         if self.controller is not None:
-            self.controller.prepare(self.model, self.data)     # several example controllers write qpos/qvel/ctrl here
+            # several example controllers write qpos/qvel/ctrl here
+            self.controller.prepare(self.model, self.device_data if self._device_arrays else self.data)
         return self._ensure_extractor()(self.data)
+
+    def _reset_envs(self, envs, keyframe, noise, seed, *, out=None):
+        sim = self.data.sim
+        sim.use_torch_stream()
+        mask = sim.env_mask(envs)
+        qn, qv = self._reset_noise if noise is None else (float(noise[0]), float(noise[1]))
+        key = self._reset_key if keyframe is None else self.handle._keyframe_index(keyframe)
+        self.handle.reset_envs(mask, key if key >= 0 else None, seed=self._reset_seed if seed is None else int(seed), qpos_noise=qn, qvel_noise=qv)
+        self.handle.forward_envs(mask)
+        return self.observe_device(out=out)
 
     # -- fused path ---------------------------------------------------------------------------------
     def _device_mode(self) -> int | None:
         """Kernel ctrl mode when the whole step can stay on the GPU; ``None`` when the host has to drive it."""
         if self.controller is None:
             return CTRL_KEEP
-        if self.control_decimation != 1:
+        if self.control_decimation != 1 or self._device_arrays:
             return None
         name = device_ctrl_mode_of(self.controller)
         return None if name is None else _KERNEL_MODE[name]
@@ -226,10 +272,11 @@ class Env:
 
         return all_gather_obs(local_obs, counts=list(self.shard.counts), single_rank=True)
 
-    def observe_device(self, gather: bool = False):
-        """Flat observation ``[batch, obs_dim]`` of the current state as a torch tensor on the GPU (``ObservationExtractor.gather_device``);
-        ``gather=True`` on a sharded environment: the all-gathered ``[GLOBAL batch, obs_dim]``."""
-        obs = self._ensure_extractor().gather_device(self.data)
+    def observe_device(self, gather: bool = False, *, out=None):
+        """Flat observation ``[batch, obs_dim]`` of the current state as a torch tensor on the GPU (``ObservationExtractor.gather_device``;
+        ``out``: the tensor to fill, else the extractor's reused buffer); ``gather=True`` on a sharded environment: the all-gathered
+        ``[GLOBAL batch, obs_dim]``."""
+        obs = self._ensure_extractor().gather_device(self.data, out=out)
         return self.gather_observations(obs) if gather else obs
 
     def rollout(self, nsteps: int, *, obs_every: int = 0, obs_out=None, obs_spec_handle=None, gather: bool = False):
@@ -293,6 +340,60 @@ class Env:
         if jacs:
             info["jacobians"] = _one_or_all(jacs)
 
+    # -- device-resident path: torch controller on the GPU state ---------------------------------------------------------------
+    def _new_obs_tensor(self):
+        import torch
+
+        spec = self._ensure_extractor().device_spec(self.data)
+        return torch.empty((self.data.batch, spec.dim), device=self.device_data.device,
+                           dtype=torch.float32 if self.data.sim.dtype == "float32" else torch.float64)
+
+    def _step_device(self, n: int, info: InfoDict, return_obs: bool) -> StepResult:
+        """``n`` physics steps with a ``device_arrays`` controller: pending host edits pushed once, then per control period the
+        controller on ``DeviceData`` and ONE ``mjb_step`` launch for the period's sub-steps, the observation gathered on the device.
+        Everything is queued on torch's current stream (the library's stream is bound to it); nothing waits for the GPU and no state
+        crosses PCIe."""
+        import torch
+
+        data, sim, dd, ctl = self.data, self.data.sim, self.device_data, self.controller
+        sim.use_torch_stream()
+        data.push_host_edits()
+        left = n
+        while left > 0:
+            phase = self._substep % self.control_decimation
+            if phase == 0:
+                ctl(self.model, dd, dd.time)
+            k = min(left, self.control_decimation - phase)
+            sim.step(k)
+            self._substep += k
+            self._device_steps += k
+            left -= k
+        data.mark_device_newer()
+        fl = sim.engine_flags_peek()                     # pinned words: what the finished launches raised, no wait
+        if fl & ~self._engine_flags_seen:                # sticky bits: the counters are fetched once per new bit
+            self._engine_flags_seen |= fl
+            data._check_engine_counters(fl)
+        ew = data.engine_warnings
+        if ew and len(ew) > self._engine_warnings_reported:
+            info["engine_warnings"] = list(ew[self._engine_warnings_reported:])
+            self._engine_warnings_reported = len(ew)
+        obs = self.observe_device(out=self._new_obs_tensor()) if (return_obs or self.reset_done) else None
+        reward = self.reward_fn(self.model, dd, obs) if self.reward_fn else None
+        done = None
+        if self.done_fn:
+            done = torch.as_tensor(self.done_fn(self.model, dd, obs), device=dd.device).to(torch.bool).reshape(self.data.batch)
+        else:
+            done = torch.zeros(self.data.batch, dtype=torch.bool, device=dd.device)
+        if self.reset_done:
+            info["final_observation"] = obs
+            obs = self._reset_envs(done, None, None, None, out=self._new_obs_tensor())
+        if self.info_fn:
+            for key, value in self.info_fn(self.model, dd, obs).items():
+                if key in info:
+                    raise TemplateError(f"info key collision: {key}")
+                info[key] = value
+        return StepResult(obs=obs if return_obs else None, reward=reward, done=done, info=info)
+
     def step(self, n: int = 1, *, return_obs: bool = True) -> StepResult:
         if n < 1:
             raise ConfigError("Env.step(n): n must be >= 1")
@@ -300,6 +401,8 @@ class Env:
         if self._compat_warnings and not self._warnings_reported:
             info["compat_warnings"] = list(self._compat_warnings)
             self._warnings_reported = True
+        if self._device_arrays:
+            return self._step_device(n, info, return_obs)
         if self.controller is not None and self._device_mode() is not None:
             self.rollout(n)                        # controller + n steps in one launch
             self.data.sync_host()

@@ -304,13 +304,14 @@ class MjData:
     def sync_host(self) -> None:
         self._pull("qpos")
 
-    def _check_engine_counters(self) -> None:
+    def _check_engine_counters(self, word: int | None = None) -> None:
         """Surface truncated physics once: contacts / constraint rows beyond the LDS caps, bad-state auto-resets (the device
-        counters).  Cheap: one sticky flags word rides along with every mirror refresh; the [batch, 8] counters are
-        only fetched once it is non-zero."""
-        if int(self._flags[0]) == 0:
+        counters).  Cheap: one sticky flags word rides along with every mirror refresh (``word``: the caller read it
+        elsewhere, e.g. ``BatchSim.engine_flags_peek``); the [batch, 8] counters are only fetched once it is non-zero."""
+        fl = int(self._flags[0]) if word is None else int(word)
+        if fl == 0:
             return
-        if int(self._flags[0]) & 8:
+        if fl & 8:
             raise TemplateError("the step kernel's work scheduler gave up waiting for a chunk of steps (engine flag 8): the results of "
                                 "this launch are invalid; set MJB_CHUNK_STEPS=0 to use the static map and report the configuration")
         cn = self._sim.counters()

@@ -87,6 +87,21 @@ class ModelHandle:
     def reset_keyframe(self, key: int | str) -> None:
         mj.mj_resetDataKeyframe(self.model, self.data, self._keyframe_index(key))
 
+    # -- per-environment lifecycle: device-side mask, no host synchronisation ------------------------------------------------------
+    def reset_envs(self, mask=None, key: int | str | None = None, *, seed: int = 0, qpos_noise: float = 0.0, qvel_noise: float = 0.0) -> None:
+        """mj_resetData / mj_resetDataKeyframe of the environments in ``mask`` only (``BatchSim.reset_envs``: torch bool / uint8 [batch] on
+        the data's GPU, an index sequence or a numpy bool mask; ``None`` = all), with optional uniform reset noise.  The derived arrays of
+        those environments are stale until :meth:`forward_envs`."""
+        self.data.push_host_edits()
+        self.data.sim.reset_envs(mask, key=-1 if key is None else self._keyframe_index(key), seed=seed, qpos_noise=qpos_noise, qvel_noise=qvel_noise)
+        self.data.mark_device_newer()
+
+    def forward_envs(self, mask=None) -> None:
+        """mj_forward of the environments in ``mask`` only; the others keep every array."""
+        self.data.push_host_edits()
+        self.data.sim.forward_envs(mask)
+        self.data.mark_device_newer()
+
     def _keyframe_index(self, key: int | str) -> int:
         if isinstance(key, str):
             found = mj.mj_name2id(self.model, mj.mjtObj.mjOBJ_KEY, key)
