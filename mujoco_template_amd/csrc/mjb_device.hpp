@@ -245,11 +245,7 @@ template <typename T> MJB_DEV void cross3(T* r, const T* a, const T* b) {
 // frame).  float64 keeps sqrt and division (the validation path is held to 1e-12 against the oracle).
 template <typename T> MJB_DEV T normalize3(T* a) {
   const T n2 = dot3(a, a);
-#ifdef MJB_R2_KINEMATICS
-  if constexpr (false) {
-#else
   if constexpr (sizeof(T) == 4) {
-#endif
     if (n2 < Num<T>::minval() * Num<T>::minval()) { a[0] = 1; a[1] = 0; a[2] = 0; return t_sqrt(n2); }
     const T s = t_rsqrt(n2);
     a[0] *= s; a[1] *= s; a[2] *= s;
@@ -277,11 +273,7 @@ template <typename T> MJB_DEV void quat_mul(T* r, const T* a, const T* b) {
 }
 template <typename T> MJB_DEV void quat_normalize(T* q) {
   const T n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-#ifdef MJB_R2_KINEMATICS
-  if constexpr (false) {
-#else
   if constexpr (sizeof(T) == 4) {
-#endif
     if (n2 < Num<T>::minval() * Num<T>::minval()) { q[0] = 1; q[1] = q[2] = q[3] = 0; return; }
     const T s = t_rsqrt(n2);
     q[0] *= s; q[1] *= s; q[2] *= s; q[3] *= s;
@@ -570,11 +562,6 @@ MJB_DEV void tile_factor(MRef m, const T* M, T* W, T* dinv, T* col, const T* J, 
   ModelRef<T> m = MJB_MODEL_OF(mp_); LayRef L = *lp_;  \
   MJB_SPEC_ASSUME(m) MJB_SPEC_ASSUME_LAY(L)
 #endif
-#if defined(MJB_PROFILE) && !defined(MJB_HOST_EMU)
-#define MJB_STAMP(c, k) do { unsigned long long t_ = __builtin_amdgcn_s_memtime(); (c).pacc[k] += t_ - (c).pt; (c).pt = t_; } while (0)
-#else
-#define MJB_STAMP(c, k) ((void)0)
-#endif
 template <typename T> using ModelRef = const DevModel<T> MJB_CONST&;
 typedef const Lay MJB_CONST& LayRef;
 
@@ -596,12 +583,44 @@ template <typename T> struct Ctx {
   MJB_DEVM Ctx(const DevModel<T> MJB_CONST* m_, const Lay MJB_CONST* L_, T* w_, int* wi_, int lane_) : mp(m_), lp(L_), w(w_), wi(wi_), lane(lane_), ncon(0), nefc(0), niter(0), con_dropped(0), efc_dropped(0) {}
 };
 
-// Diagnostic build -DMJB_PHASE_REPEAT: how many times an idempotent piece of the solver runs (ids 32.. name the pieces; 1 in the product)
-#if defined(MJB_PHASE_REPEAT) && !defined(MJB_HOST_EMU)
-#define MJB_REP_N(c, id) ((c).rep == (id) ? 2 : 1)
+// ---------------------------------------------------------------------------
+// Hooks of the diagnostic builds, all of them no-ops in the product kernel:
+//  -DMJB_PROFILE (make prof, scripts/gpu_phase_profile.py): in-kernel cycle stamps.  MJB_STAMP(c, k) adds the shader cycles since
+//    the previous stamp (MJB_STAMP_START: the first) to phase k, MJB_TIMED(c, k, call) those of one call, MJB_COUNT(c, k) counts an
+//    event; MJB_PACC(c, k) is where a solver routine adds its own sub-phase cycles (nullptr: nowhere).  MJB_PROF_FLUSH adds the
+//    sums of the environment to DevData::prof.
+//  -DMJB_PHASE_REPEAT (scripts/gpu_phase_pmc.py): the phase whose index equals StepArgs::repeat_phase (MJB_SET_REPEAT) runs TWICE:
+//    MJB_PHASE_CALL(c, k, call), or MJB_REP_N(c, id) passes of a piece of the solver (ids REP_* name the pieces).  Every such phase
+//    recomputes its outputs from LDS inputs it does not modify (idempotent), so the state evolves exactly as in the product kernel
+//    and the DIFFERENCE of the hardware counters of two passes (repeat k vs no repeat) is phase k's own instruction count,
+//    active-lane cycles and executed flops.
+//  -DMJB_TIMELINE (scripts/gpu_timeline.py): per-workgroup records, kept by k_step_body (mjb_kernels.hpp) in the accumulator that
+//    env_run receives as tlacc (null otherwise).
+// ---------------------------------------------------------------------------
+#if defined(MJB_PROFILE) && !defined(MJB_HOST_EMU)
+#define MJB_STAMP_START(c) ((c).pt = __builtin_amdgcn_s_memtime())
+#define MJB_STAMP(c, k) do { unsigned long long t_ = __builtin_amdgcn_s_memtime(); (c).pacc[k] += t_ - (c).pt; (c).pt = t_; } while (0)
+#define MJB_TIMED(c, k, call) do { unsigned long long t0_ = __builtin_amdgcn_s_memtime(); call; (c).pacc[k] += __builtin_amdgcn_s_memtime() - t0_; } while (0)
+#define MJB_COUNT(c, k) ((c).pacc[k] += 1)
+#define MJB_PACC(c, k) ((c).pacc + (k))
+#define MJB_PROF_FLUSH(c, prof, lane) do { if ((lane) == 0 && (prof)) for (int k_ = 0; k_ < PH_N; k_++) atomicAdd((prof) + k_, (c).pacc[k_]); } while (0)
 #else
-#define MJB_REP_N(c, id) 1
+#define MJB_STAMP_START(c) ((void)0)
+#define MJB_STAMP(c, k) ((void)0)
+#define MJB_TIMED(c, k, call) do { call; } while (0)
+#define MJB_COUNT(c, k) ((void)0)
+#define MJB_PACC(c, k) nullptr
+#define MJB_PROF_FLUSH(c, prof, lane) ((void)0)
 #endif
+#if defined(MJB_PHASE_REPEAT) && !defined(MJB_HOST_EMU)
+#define MJB_SET_REPEAT(c, k) ((c).rep = (k))
+#define MJB_REPEATS(c, k) ((c).rep == (k))
+#else
+#define MJB_SET_REPEAT(c, k) ((void)0)
+#define MJB_REPEATS(c, k) false
+#endif
+#define MJB_REP_N(c, id) (MJB_REPEATS(c, id) ? 2 : 1)
+#define MJB_PHASE_CALL(c, k, call) do { call; if (MJB_REPEATS(c, k)) { gsync<G>(); call; } } while (0)
 enum { REP_CHOL = 32, REP_REUSE = 33, REP_MV = 34, REP_LS = 35, REP_WARM = 36, REP_GRAD = 37, REP_CTRL = 38 };
 
 // ---------------------------------------------------------------------------
@@ -671,15 +690,6 @@ MJB_DEV void reg_factor32(MRef m, const T* M, T* W, T* dinv, const T* J, const T
 // one MFMA per pair of constraint rows.  Forward substitution is fused; L goes to LDS (packed) for the
 // backward substitution and for reuse when the active set does not change.
 // ---------------------------------------------------------------------------
-#ifndef MJB_PANEL4
-#define MJB_PANEL4 0             // experiment (round 3, off): FOUR pivots per panel in the MFMA sweep inverse instead of two.  Measured in
-#endif                           // scripts/micro/factor_bench (profiles/r03_panel4_microbench.log): panel loop 4682 -> 4374 cycles alone, 5210 -> 4595 with two
-                                 // waves per SIMD, same residual - about 1 % of a step.  Not adopted: a wave issues one VALU instruction per >= 4 cycles
-                                 // whatever it does, and the 4x4 scalar elimination (10 v_readlane, 4 rcp, 20 dependent FMAs) costs as many instructions
-                                 // per pivot as two 2x2 ones; halving the MFMA round trips alone buys little, and the rounding of every solve would change.
-#ifndef MJB_SWEEP_EXCLUDE
-#define MJB_SWEEP_EXCLUDE 1      // factor_W mode that keeps the Cholesky path (1 = Hessian); -1: sweep everywhere
-#endif
 #ifndef MJB_HOST_EMU
 MJB_DEV float half_bcast(float v, int half) {     // value of the given 32-lane half, column-aligned, in all 64 lanes
   auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
@@ -770,7 +780,7 @@ MJB_DEV void mfma_solve32(const float* W, const float* dinv, float* x, int n, in
   if (h == 0 && c_ < n) x[c_] = r;
   gsync<64>();
 }
-// ---- round 3: the accumulator in ELIMINATION ORDER -------------------------------------------------------------------------------
+// ---- the accumulator in ELIMINATION ORDER ---------------------------------------------------------------------------------------
 // The hardware fixes which accumulator row a (register, half) pair holds: register 4q+t, half h <-> row 8q+4h+t.  Which MATRIX index
 // sits on accumulator row / column rho is ours to choose, as long as rows and columns use the same map (a symmetric relabelling).
 // With  pos(rho) = 8q + 2t + h  register i holds matrix rows 2i (lanes 0..31) and 2i+1 (lanes 32..63): the two pivot columns of panel
@@ -779,12 +789,12 @@ MJB_DEV void mfma_solve32(const float* W, const float* dinv, float* x, int n, in
 // outside the panel loop.  The factor that lands in LDS is the ordinary Cholesky factor in natural order (only lanes were relabelled).
 MJB_DEVM constexpr int acc_pos(int c) { return (c & 24) | ((c & 3) << 1) | ((c >> 2) & 1); }       // matrix index of accumulator row / column c
 MJB_DEVM constexpr int acc_lane(int p) { return (p & 24) | ((p & 1) << 2) | ((p >> 1) & 3); }      // its inverse
-// Second change: the right-hand side rides along as row / column n of the matrix (n < 32).  Cholesky of [A b; b^T 1] has y^T = (L^-1 b)^T
+// Second: the right-hand side rides along as row / column n of the matrix (n < 32).  Cholesky of [A b; b^T 1] has y^T = (L^-1 b)^T
 // as row n of its factor, so the forward substitution IS the trailing update (the same MFMA) - no per-panel v_readlane / FMA / select
 // chain for it.  y is stored like any row of the factor (to ybuf) by the lane that stands for column n.
 // Third: nothing is masked on the way into the MFMA.  Columns already eliminated hold rounding residue instead of zeros; it only ever
 // feeds dead rows / columns (operand lane rho touches accumulator row rho, operand lane gamma column gamma).  Only the stores to LDS
-// are predicated.  The factor L is bitwise the one of the round-2 form (same pivots, same FMAs on the live entries).
+// are predicated.  The factor L is bitwise that of the natural-order elimination (same pivots, same FMAs on the live entries).
 template <typename MRef>
 MJB_DEV void mfma_factor32(MRef m, const float* M, float* W, float* dinv, float* ybuf, const float* J, const float* dw, int nefc, int mode, int n, int lane, float* x, unsigned long long* pf = nullptr) {
   const int h = lane >> 5, c_ = lane & 31, pc = acc_pos(c_);
@@ -886,109 +896,8 @@ MJB_DEV void mfma_factor32(MRef m, const float* M, float* W, float* dinv, float*
   }
   if (pf) { unsigned long long tq3 = MJB_MEMTIME(); pf[0] += tq1 - tq0; pf[1] += tq2 - tq1; pf[2] += tq3 - tq2; }
 }
-// the round-2 form (natural lane order, fused forward substitution in registers): kept for A/B runs (-DMJB_R2_FACTOR)
-template <typename MRef>
-MJB_DEV void mfma_factor32_r2(MRef m, const float* M, float* W, float* dinv, const float* J, const float* dw, int nefc, int mode, int n, int lane, float* x, unsigned long long* pf = nullptr) {
-  const int h = lane >> 5, c_ = lane & 31;
-  unsigned long long tq0 = pf ? MJB_MEMTIME() : 0;
-  mjb_f16v acc;
-  {
-    // acc[4q+t] of lane (h, c) = A[8q+4h+t][c] = A[c][8q+4h+t] (symmetric): every lane reads along its own row of M,
-    // so the 16 LDS reads use one address register and immediate offsets.  Rows/columns >= n are padded with identity.
-    const int c = c_;
-    const bool cin = c < n;
-    const float* Mc = M + (cin ? c : 0) * n + 4 * h;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int k = 8 * (i >> 2) + (i & 3);                    // this register holds row k + 4 h
-      const float mv = Mc[k];                                  // may read past row c when the row is >= n: masked
-      // Round 3: one SHARED lane mask (c < n) for the registers whose rows exist in both halves (k + 4 < n: a uniform test, a
-      // compile-time one in the specialised kernel); only the last registers need the per-row test, and only they can hold the
-      // identity padding.  (The round-2 form built two lane masks per register - 32 SGPR pairs the compiler hoisted out of the step
-      // loop and kept spilled in VGPR lanes: two v_readlane + a hazard nop per use.)  Same values bit for bit.
-      float v;
-      if (k + 4 < n) v = cin ? mv : 0.0f;
-      else v = (cin && k + 4 * h < n) ? mv : 0.0f;
-      if (mode == 2) { if (k + 4 * h == c) v += cin ? m.timestep * m.dof_damping[c] : 1.0f; }      // + h D on the diagonal (identity on the padding)
-      else if (k + 4 >= n) { if (k + 4 * h == c && !cin) v += 1.0f; }                              // identity padding of rows / columns >= n
-      acc[i] = v;
-    }
-    if (mode == 1) {
-      // Hessian M + J^T D J: one rank-2 MFMA per PAIR OF ACTIVE ROWS (D != 0), the next pair's J loads in flight
-      // while the current MFMA runs.
-      const int cm = c < n ? c : 0;
-      for (int base = 0; base < nefc; base += 64) {
-        const int rix = base + lane;
-        const float dl = rix < nefc ? dw[rix] : 0.0f;
-        unsigned long long act = MJB_BALLOT(dl != 0.0f);
-        float jcur = 0.0f, dcur = 0.0f;
-        bool have = false;
-        while (act) {
-          int ra = __builtin_ctzll(act); act &= act - 1;
-          int rb = ra; float dB = 0.0f;
-          if (act) { rb = __builtin_ctzll(act); act &= act - 1; dB = rdlane_f(dl, rb); }
-          float dA = rdlane_f(dl, ra);
-          int rr = h == 0 ? ra : rb;
-          float jn = J[(base + rr) * n + cm];
-          float dn = h == 0 ? dA : dB;
-          if (have) acc = MJB_MFMA(dcur * jcur, jcur, acc);
-          jcur = c < n ? jn : 0.0f; dcur = dn; have = true;
-        }
-        if (have) acc = MJB_MFMA(dcur * jcur, jcur, acc);
-      }
-    }
-  }
-  float r = (x && c_ < n) ? x[c_] : 0.0f;                     // RHS replicated in both halves (lane -> row c)
-  float myinv = 1.0f;
-  const int wrow = tri_at(c_, 0), cvalid = (h == 0 && c_ < n) ? 0 : -1;
-  float* const wrowp = W + wrow;
-  float* const dumpp = dinv + n;                              // one spare word behind dinv swallows the masked stores
-  unsigned long long tq1 = pf ? MJB_MEMTIME() : 0;
-#pragma unroll
-  for (int jb = 0; jb < 16; jb++) {
-    const int j0 = 2 * jb, j1 = j0 + 1, hj = (j0 >> 2) & 1, ij = 4 * (j0 >> 3) + (j0 & 3);
-    if (j0 >= n) continue;                                    // padded (identity) columns: nothing to eliminate (uniform skip)
-    int c = c_;
-    MJB_OPAQUE1(c);                               // keep the per-column lane compares in the loop (cheaper than spilled masks)
-    // columns j0, j1 of the trailing matrix, one entry per lane; the 2x2 pivot block [a b; b d] is eliminated in scalars
-    // so that the serial chain per panel is rsq -> fma -> rsq
-    float v0 = half_bcast(acc[ij], hj), v1r = half_bcast(acc[ij + 1], hj);
-    float a = __builtin_fmaxf(rdlane_f(v0, j0), Num<float>::minval()), b = rdlane_f(v0, j1), d = rdlane_f(v1r, j1);
-    float inv0 = MJB_RSQF(a), bia = b * inv0 * inv0;            // v_rsq_f32: 1 ulp, no refinement step on the chain
-    float d1 = __builtin_fmaxf(d - b * bia, Num<float>::minval());
-    float inv1 = MJB_RSQF(d1);
-    float v1 = v1r - bia * v0;
-    // lane j0 of v0 IS the pivot a (lane j1 of v1 is d1), so the diagonal needs no case of its own: one compare + select per column
-    // instead of two (bitwise the same unless a pivot fell below the 1e-15 clamp, which an SPD Hessian >= M never does)
-    float L0 = c >= j0 ? v0 * inv0 : 0.0f;
-    float L1 = c >= j1 ? v1 * inv1 : 0.0f;
-    myinv = c == j0 ? inv0 : (c == j1 ? inv1 : myinv);
-    // fused forward substitution
-    float y0 = rdlane_f(r, j0) * inv0;
-    float y1 = (rdlane_f(r, j1) - b * inv0 * y0) * inv1;
-    r = c > j1 ? r - L0 * y0 - L1 * y1 : (c == j1 ? y1 : (c == j0 ? y0 : r));
-    // packed factor to LDS for the backward substitution / later reuse; masked lanes write the dump word
-    int cc = c | cvalid;
-    float* p0 = cc >= j0 ? wrowp : dumpp - j0;                // select between two lane-constant pointers: the column index
-    float* p1 = cc >= j1 ? wrowp : dumpp - j1;                // rides in the DS instruction's immediate offset
-    p0[j0] = L0;
-    p1[j1] = L1;
-    // rank-2 trailing update of the whole matrix: acc -= [L0 L1] [L0 L1]^T
-    float av = h == 0 ? L0 : L1;
-    acc = MJB_MFMA(-av, av, acc);
-  }
-  unsigned long long tq2 = pf ? MJB_MEMTIME() : 0;
-  if (h == 0 && c_ < n) dinv[c_] = myinv;
-  gsync<64>();
-  if (x) {                                                    // backward substitution L^T x = y from the packed factor in LDS
-    float rs = mfma_backward32(W, n, c_, myinv, r);
-    if (h == 0 && c_ < n) x[c_] = rs;
-    gsync<64>();
-  }
-  if (pf) { unsigned long long tq3 = MJB_MEMTIME(); pf[0] += tq1 - tq0; pf[1] += tq2 - tq1; pf[2] += tq3 - tq2; }
-}
 // x <- A^-1 x for A = M (mode 0), M + J^T D_active J (mode 1, D in dw) or M + h diag(damping) (mode 2), n <= 32, fp32.
-// The symmetric matrix lives in one 32x32 MFMA accumulator (lane (h,c): column c, rows 8q+4h+t) and is inverted in place
+// The symmetric matrix lives in one 32x32 MFMA accumulator (in elimination order, acc_pos above) and is inverted in place
 // by the symmetric SWEEP operator, two pivots per v_mfma_f32_32x32x2_f32:
 //     B_ij <- B_ij - U_i P^-1 U_j^T,   B_iP <- U_i P^-1,   B_PP <- -P^-1        (U = columns j0,j1;  P = their 2x2 pivot block)
 // With U' = U - [e_j0 e_j1] the MFMA operands  A_op = -U' P^-1,  B_op = U'^T  produce the pivot rows/columns as well; only the
@@ -997,8 +906,7 @@ MJB_DEV void mfma_factor32_r2(MRef m, const float* M, float* W, float* dinv, con
 // is one register (+ a half swap) at every step.
 // Two halves, so that the two-wave step kernel (k_step2) can invert M + h D while the other wave still solves the constraints:
 // mfma_sweep_invert32 leaves -A^-1 in the accumulator, mfma_sweep_apply32 is the mat-vec.  mfma_sweep_solve32 = both.
-#ifndef MJB_R2_FACTOR
-// Round 3: the accumulator in elimination order (acc_pos above): the two pivot columns of panel jb are register jb, stacked
+// In elimination order the two pivot columns of panel jb are register jb, stacked
 // [u0 | u1] - which is the B operand U'^T itself once the two pivot lanes have had their 1 subtracted (and the register that goes on
 // living is that minus the same indicator again: the "-2" of the pivot diagonals).  One half swap hands every lane both columns for
 // the A operand.  acc = -A^-1 comes out in the same layout: register i, lane (h, c) = -A^-1[2i+h][pos(c)].
@@ -1092,162 +1000,20 @@ MJB_DEV void mfma_sweep_apply32(const mjb_f16v& acc, float* bpad, int n, int lan
   }
   if (pf) pf[2] += MJB_MEMTIME() - tq2;
 }
-#else
-template <typename MRef>
-MJB_DEV mjb_f16v mfma_sweep_invert32(MRef m, const float* M, const float* J, const float* dw, int nefc, int mode, int n, int lane, unsigned long long* pf = nullptr) {
-  const int h = lane >> 5, c_ = lane & 31;
-  unsigned long long tq0 = pf ? MJB_MEMTIME() : 0;
-  mjb_f16v acc;
-  {
-    // acc[4q+t] of lane (h, c) = A[8q+4h+t][c] = A[c][8q+4h+t] (symmetric): every lane reads along its own row of M,
-    // so the 16 LDS reads use one address register and immediate offsets.  Rows/columns >= n are padded with identity.
-    const int c = c_;
-    const bool cin = c < n;
-    const float* Mc = M + (cin ? c : 0) * n + 4 * h;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int k = 8 * (i >> 2) + (i & 3);                    // this register holds row k + 4 h
-      const float mv = Mc[k];                                  // may read past row c when the row is >= n: masked
-      // Round 3: one SHARED lane mask (c < n) for the registers whose rows exist in both halves (k + 4 < n: a uniform test, a
-      // compile-time one in the specialised kernel); only the last registers need the per-row test, and only they can hold the
-      // identity padding.  (The round-2 form built two lane masks per register - 32 SGPR pairs the compiler hoisted out of the step
-      // loop and kept spilled in VGPR lanes: two v_readlane + a hazard nop per use.)  Same values bit for bit.
-      float v;
-      if (k + 4 < n) v = cin ? mv : 0.0f;
-      else v = (cin && k + 4 * h < n) ? mv : 0.0f;
-      if (mode == 2) { if (k + 4 * h == c) v += cin ? m.timestep * m.dof_damping[c] : 1.0f; }      // + h D on the diagonal (identity on the padding)
-      else if (k + 4 >= n) { if (k + 4 * h == c && !cin) v += 1.0f; }                              // identity padding of rows / columns >= n
-      acc[i] = v;
-    }
-    if (mode == 1) {
-      // Hessian M + J^T D J: one rank-2 MFMA per PAIR OF ACTIVE ROWS (D != 0), the next pair's J loads in flight
-      // while the current MFMA runs.
-      const int cm = c < n ? c : 0;
-      for (int base = 0; base < nefc; base += 64) {
-        const int rix = base + lane;
-        const float dl = rix < nefc ? dw[rix] : 0.0f;
-        unsigned long long act = MJB_BALLOT(dl != 0.0f);
-        float jcur = 0.0f, dcur = 0.0f;
-        bool have = false;
-        while (act) {
-          int ra = __builtin_ctzll(act); act &= act - 1;
-          int rb = ra; float dB = 0.0f;
-          if (act) { rb = __builtin_ctzll(act); act &= act - 1; dB = rdlane_f(dl, rb); }
-          float dA = rdlane_f(dl, ra);
-          int rr = h == 0 ? ra : rb;
-          float jn = J[(base + rr) * n + cm];
-          float dn = h == 0 ? dA : dB;
-          if (have) acc = MJB_MFMA(dcur * jcur, jcur, acc);
-          jcur = c < n ? jn : 0.0f; dcur = dn; have = true;
-        }
-        if (have) acc = MJB_MFMA(dcur * jcur, jcur, acc);
-      }
-    }
-  }
-  unsigned long long tq1 = pf ? MJB_MEMTIME() : 0;
-#if MJB_PANEL4
-  // FOUR pivots per panel (experiment, see MJB_PANEL4 above).  Columns j0..j0+3 are rows 8q+4h+t of ONE half, registers 4q..4q+3.
-  // Block elimination  B <- B - U P^-1 U^T  with P = L D L^T (unit lower L, in scalars):  W = U' L^-T  (per lane: three dependent
-  // FMAs),  Z = W D^-1,  B -= Z W^T  as two rank-2 MFMAs;  U' = U - [e_j0 .. e_j3] makes the same products deliver the pivot rows /
-  // columns and -P^-1 up to a -2 on the four pivot diagonals (as in the two-pivot form).
-#pragma unroll
-  for (int jq = 0; jq < 8; jq++) {
-    const int j0 = 4 * jq, hj = jq & 1, ij = 4 * (jq >> 1);
-    if (j0 >= n) continue;                                    // padded (identity) columns: nothing to eliminate (uniform skip)
-    int c = c_, ln = lane;
-    MJB_OPAQUE2(c, ln);                     // keep the per-column lane compares in the loop (cheaper than spilled masks)
-    const float u0 = half_bcast(acc[ij], hj), u1 = half_bcast(acc[ij + 1], hj), u2 = half_bcast(acc[ij + 2], hj), u3 = half_bcast(acc[ij + 3], hj);
-    const float tiny = Num<float>::minval();
-    const float a00 = __builtin_fmaxf(rdlane_f(u0, j0), tiny), a10 = rdlane_f(u0, j0 + 1), a20 = rdlane_f(u0, j0 + 2), a30 = rdlane_f(u0, j0 + 3);
-    const float a11 = rdlane_f(u1, j0 + 1), a21 = rdlane_f(u1, j0 + 2), a31 = rdlane_f(u1, j0 + 3);
-    const float a22 = rdlane_f(u2, j0 + 2), a32 = rdlane_f(u2, j0 + 3), a33 = rdlane_f(u3, j0 + 3);
-    const float i0 = MJB_RCPF(a00);
-    const float l10 = a10 * i0, l20 = a20 * i0, l30 = a30 * i0;
-    const float d1 = __builtin_fmaxf(a11 - l10 * a10, a11 * tiny), i1 = MJB_RCPF(d1);
-    const float t21 = a21 - l20 * a10, t31 = a31 - l30 * a10;
-    const float l21 = t21 * i1, l31 = t31 * i1;
-    const float d2 = __builtin_fmaxf(a22 - l20 * a20 - l21 * t21, a22 * tiny), i2 = MJB_RCPF(d2);
-    const float t32 = a32 - l30 * a20 - l31 * t21;
-    const float l32 = t32 * i2;
-    const float d3 = __builtin_fmaxf(a33 - l30 * a30 - l31 * t31 - l32 * t32, a33 * tiny), i3 = MJB_RCPF(d3);
-    const float w0 = c == j0 ? u0 - 1.0f : u0;
-    const float w1 = (c == j0 + 1 ? u1 - 1.0f : u1) - l10 * w0;
-    const float w2 = (c == j0 + 2 ? u2 - 1.0f : u2) - l20 * w0 - l21 * w1;
-    const float w3 = (c == j0 + 3 ? u3 - 1.0f : u3) - l30 * w0 - l31 * w1 - l32 * w2;
-#pragma unroll
-    for (int t = 0; t < 4; t++) acc[ij + t] -= ln == 32 * hj + j0 + t ? 2.0f : 0.0f;
-    acc = MJB_MFMA(h == 0 ? -(w0 * i0) : -(w1 * i1), h == 0 ? w0 : w1, acc);
-    acc = MJB_MFMA(h == 0 ? -(w2 * i2) : -(w3 * i3), h == 0 ? w2 : w3, acc);
-  }
-#else
-#pragma unroll
-  for (int jb = 0; jb < 16; jb++) {
-    const int j0 = 2 * jb, j1 = j0 + 1, hj = (j0 >> 2) & 1, ij = 4 * (j0 >> 3) + (j0 & 3);
-    if (j0 >= n) continue;                                    // padded (identity) columns: nothing to eliminate (uniform skip)
-    int c = c_, ln = lane;
-    MJB_OPAQUE2(c, ln);                     // keep the per-column lane compares in the loop (cheaper than spilled masks)
-    float u0 = half_bcast(acc[ij], hj), u1 = half_bcast(acc[ij + 1], hj);
-    float a = __builtin_fmaxf(rdlane_f(u0, j0), Num<float>::minval()), b = rdlane_f(u0, j1), d = rdlane_f(u1, j1);
-    float det = __builtin_fmaxf(a * d - b * b, a * Num<float>::minval());
-    float rdet = MJB_RCPF(det);
-    float p00 = d * rdet, p01 = -b * rdet, p11 = a * rdet;
-    float q0 = h == 0 ? p00 : p01, q1 = h == 0 ? p01 : p11;
-    float u0p = c == j0 ? u0 - 1.0f : u0, u1p = c == j1 ? u1 - 1.0f : u1;
-    float aop = -(u0p * q0 + u1p * q1);
-    float bop = h == 0 ? u0p : u1p;
-    acc[ij] -= ln == 32 * hj + j0 ? 2.0f : 0.0f;
-    acc[ij + 1] -= ln == 32 * hj + j1 ? 2.0f : 0.0f;
-    acc = MJB_MFMA(aop, bop, acc);
-  }
-#endif
-  if (pf) { unsigned long long tq2 = MJB_MEMTIME(); pf[0] += tq1 - tq0; pf[1] += tq2 - tq1; }
-  return acc;
-}
-// x <- A^-1 x with acc = -A^-1 from mfma_sweep_invert32 (bpad: 32 words of LDS for the zero-padded right-hand side)
-MJB_DEV void mfma_sweep_apply32(const mjb_f16v& acc, float* bpad, int n, int lane, float* x, unsigned long long* pf = nullptr) {
-  const int h = lane >> 5, c_ = lane & 31;
-  unsigned long long tq2 = pf ? MJB_MEMTIME() : 0;
-  if (h == 0) bpad[c_] = c_ < n ? x[c_] : 0.0f;               // right-hand side, zero-padded to 32
-  gsync<64>();
-  {
-    const float* bp = bpad + 4 * h;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 4; t++) { s0 += acc[t] * bp[t]; s1 += acc[4 + t] * bp[8 + t]; s2 += acc[8 + t] * bp[16 + t]; s3 += acc[12 + t] * bp[24 + t]; }
-    float s = (s0 + s1) + (s2 + s3);
-    float tot = half_sum(s);
-    if (h == 0 && c_ < n) x[c_] = -tot;                       // acc = -A^-1
-    gsync<64>();
-  }
-  if (pf) pf[2] += MJB_MEMTIME() - tq2;
-}
-#endif
 template <typename MRef>
 MJB_DEV void mfma_sweep_solve32(MRef m, const float* M, float* bpad, const float* J, const float* dw, int nefc, int mode, int n, int lane, float* x, unsigned long long* pf = nullptr) {
   const mjb_f16v acc = mfma_sweep_invert32<MRef>(m, M, J, dw, nefc, mode, n, lane, pf);
   mfma_sweep_apply32(acc, bpad, n, lane, x, pf);
 }
-template <typename MRef>
-MJB_DEV void mfma_sweep_solve32(MRef, const double*, double*, const double*, const double*, int, int, int, int, double*, unsigned long long* = nullptr) {}
-template <typename MRef>
-MJB_DEV void mfma_factor32(MRef, const double*, double*, double*, double*, const double*, const double*, int, int, int, int, double*, unsigned long long* = nullptr) {}
-template <typename MRef>
-MJB_DEV void mfma_factor32_r2(MRef, const double*, double*, double*, const double*, const double*, int, int, int, int, double*, unsigned long long* = nullptr) {}
-MJB_DEV void mfma_solve32(const double*, const double*, double*, int, int) {}
 
 // W <- Cholesky factor of M (mode 0), M + J^T D_active J (mode 1, dw in efc_jv) or M + h diag(damping) (mode 2)
 // If x != nullptr the system (factor) x = x is solved in the same pass (fused on the register path).
 template <typename T, int G> MJB_DEV void factor_W_impl(Ctx<T>& c, int mode, T* x);
-// true where factor_W() inverts-and-solves in registers (fp32, one wave per environment, nv <= 32) and leaves NO factor in W
+// true where factor_W() runs in registers (fp32, one wave per environment, nv <= 32): the Hessian's factor it leaves in W is the
+// packed one of mfma_factor32, which mfma_solve32 reuses (M and M + hD are swept and leave none)
 template <typename T, int G> MJB_DEV bool fused_inverse_path(int nv) { return G == 64 && sizeof(T) == 4 && nv <= 32; }
 template <typename T, int G> MJB_DEV void factor_W(Ctx<T>& c, int mode, T* x) {
-#if defined(MJB_PROFILE) && !defined(MJB_HOST_EMU)
-  unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-  factor_W_impl<T, G>(c, mode, x);
-  c.pacc[PH_FAC_ALL] += __builtin_amdgcn_s_memtime() - t0_;   // informational: already inside the enclosing phase's stamp
-#else
-  factor_W_impl<T, G>(c, mode, x);
-#endif
+  MJB_TIMED(c, PH_FAC_ALL, (factor_W_impl<T, G>(c, mode, x)));   // informational: already inside the enclosing phase's stamp
 }
 template <typename T, int G> MJB_DEV void factor_W_impl(Ctx<T>& c, int mode, T* x) {
   MJB_ENV(c); T* w = c.w; const int lane = c.lane, nv = m.nv, nefc = c.nefc;
@@ -1256,18 +1022,11 @@ template <typename T, int G> MJB_DEV void factor_W_impl(Ctx<T>& c, int mode, T* 
     if (nv <= 32) {
       // M and M + hD are well conditioned: in-register sweep inverse.  The Hessian (contact stiffness on a few dofs) keeps
       // the backward-stable Cholesky, whose packed factor in W is reused while the active set does not change.
-#if defined(MJB_PROFILE)
-      unsigned long long* pf = c.pacc + PH_FAC_LOAD;
-#else
-      unsigned long long* pf = nullptr;
-#endif
-      if (sizeof(T) == 4 && mode != MJB_SWEEP_EXCLUDE) mfma_sweep_solve32<ModelRef<T>>(m, M, w + L.tmp, J, dw, nefc, mode, nv, lane, x, pf);
-#ifdef MJB_R2_FACTOR
-      else if (sizeof(T) == 4) mfma_factor32_r2<ModelRef<T>>(m, M, W, w + L.tmp, J, dw, nefc, mode, nv, lane, x, pf);
-#else
-      else if (sizeof(T) == 4) mfma_factor32<ModelRef<T>>(m, M, W, w + L.tmp, w + L.cholcol, J, dw, nefc, mode, nv, lane, x, pf);
-#endif
-      else reg_factor32<T, ModelRef<T>>(m, M, W, w + L.tmp, J, dw, nefc, mode, nv, lane, x);
+      if constexpr (sizeof(T) == 4) {
+        unsigned long long* pf = MJB_PACC(c, PH_FAC_LOAD);
+        if (mode != 1) mfma_sweep_solve32<ModelRef<T>>(m, M, w + L.tmp, J, dw, nefc, mode, nv, lane, x, pf);
+        else mfma_factor32<ModelRef<T>>(m, M, W, w + L.tmp, w + L.cholcol, J, dw, nefc, mode, nv, lane, x, pf);
+      } else reg_factor32<T, ModelRef<T>>(m, M, W, w + L.tmp, J, dw, nefc, mode, nv, lane, x);
       return;
     }
     tile_factor<T, 8, ModelRef<T>>(m, M, W, w + L.tmp, w + L.cholcol, J, dw, nefc, mode, nv, lane);
@@ -1485,7 +1244,7 @@ template <typename T, int G> MJB_DEV void kinematics(Ctx<T>& c) {
   }
   gsync<G>();
   // (2) compose down the tree, in place.
-  // Round 3: POINTER JUMPING instead of one pass per tree level.  The per-level loop ran nlevel (humanoid: 7) dependent rounds with
+  // POINTER JUMPING instead of one pass per tree level (A/B in DESIGN.md §5).  The per-level loop ran nlevel (humanoid: 7) dependent rounds with
   // one to four lanes active each (mean 7.3 active lanes over the whole phase, profiles/r03_phase_table.txt: the worst of the
   // kernel) - ~105 instructions per level whatever the number of bodies in it.  Rigid transforms compose associatively, so every
   // body can instead double the distance to the ancestor its pose is relative to: round r composes the pose of body b (relative
@@ -1494,11 +1253,7 @@ template <typename T, int G> MJB_DEV void kinematics(Ctx<T>& c) {
   // reads all its inputs, syncs, then writes.  The unit quaternion is re-normalised ONCE per body at the end (the level loop did
   // it per level, like mj_kinematics; the product of unit quaternions stays unit to rounding) - results differ from the
   // sequential composition in the last bits only (float64 instantiation vs the oracle: <= 1e-15).
-#ifdef MJB_R2_KINEMATICS                                            // A/B timing against the round-2 form (scripts/gpu_perf_quick.py)
-  if (false) {
-#else
   if (m.nbody - 1 <= G) {
-#endif
     const int b = 1 + lane, nl = m.nlevel;
     const bool own = b < m.nbody;
     const int dep = own ? m.body_depth[b] : 0;
@@ -2417,10 +2172,10 @@ template <typename T> MJB_DEV bool mark_active_row(int* etype, T* dw, int r, T s
   dw[r] = act ? d : (T)0;
   return ((t >> 8) & 1) != act;
 }
-template <typename T, int G> MJB_DEV T newton_direction(Ctx<T>& c, bool rebuild_wanted, T gtol2) {
+template <typename T, int G> MJB_DEV T newton_direction(Ctx<T>& c, bool rebuild, T gtol2) {
   // grad, H = M + J^T D_active J (lower, Cholesky in W), search = -H^-1 grad.  Returns |grad|^2; when that is
   // already below gtol2 the (expensive) factorisation is skipped — the caller stops iterating.
-  // The factor is rebuilt only when the active set changed since the last build (rebuild_wanted: first direction of the solve, or a row
+  // The factor is rebuilt only when the active set changed since the last build (rebuild: first direction of the solve, or a row
   // changed state in the update that produced the current point - mark_active_row).
   MJB_ENV(c); T* w = c.w; const int lane = c.lane, nv = m.nv, nefc = c.nefc;
   T *M = w + L.M, *W = w + L.W, *J = w + L.efc_J, *Ma = w + L.Ma, *force = w + L.efc_force;
@@ -2441,20 +2196,17 @@ template <typename T, int G> MJB_DEV T newton_direction(Ctx<T>& c, bool rebuild_
   }
   }
   T gn = gsum<T, G>(gpart);
-  const bool rebuild = (MJB_SWEEP_EXCLUDE != 1 && fused_inverse_path<T, G>(nv)) || rebuild_wanted;   // the sweep path keeps no factor
   gsync<G>();
   if (gn < gtol2) return gn;
-#if defined(MJB_PROFILE) && !defined(MJB_HOST_EMU)
-  c.pacc[PH_CNT_DIR] += 1; if (rebuild) c.pacc[PH_CNT_FACT] += 1;
-#endif
+  MJB_COUNT(c, PH_CNT_DIR); if (rebuild) MJB_COUNT(c, PH_CNT_FACT);
   for (int rp_ = MJB_REP_N(c, rebuild ? REP_CHOL : REP_REUSE); rp_ > 1; rp_--) {      // diagnostic build: the solve twice, right-hand side restored
     if (rebuild) factor_W<T, G>(c, 1, search);
-    else if (fused_inverse_path<T, G>(nv)) { gsync<G>(); mfma_solve32(W, w + L.tmp, search, nv, lane); }
+    else if (fused_inverse_path<T, G>(nv)) { gsync<G>(); if constexpr (sizeof(T) == 4) mfma_solve32(W, w + L.tmp, search, nv, lane); }
     for (int i = lane; i < nv; i += G) search[i] = -grad[i];
     gsync<G>();
   }
   if (rebuild) factor_W<T, G>(c, 1, search);
-  else if (fused_inverse_path<T, G>(nv)) { gsync<G>(); mfma_solve32(W, w + L.tmp, search, nv, lane); }
+  else if (fused_inverse_path<T, G>(nv)) { gsync<G>(); if constexpr (sizeof(T) == 4) mfma_solve32(W, w + L.tmp, search, nv, lane); }
   else chol_solve<T, G>(W, w + L.tmp, search, nv, lane);
   return gn;                                                   // (every solve ends with a group sync; H x = -g, so x is the direction: no negation pass)
 }
@@ -2575,9 +2327,7 @@ template <typename T, int G> MJB_DEV void solve_constraints(Ctx<T>& c) {
         else for (int r = lane; r < nefc; r += G) flip |= ((jar[r] + alpha * jv[r]) < 0) != ((jar[r] + an * jv[r]) < 0);
         const bool anyflip = gany<G>(flip);
         alpha = an;
-#if defined(MJB_PROFILE) && !defined(MJB_HOST_EMU)
-        c.pacc[PH_CNT_LS] += 1;
-#endif
+        MJB_COUNT(c, PH_CNT_LS);
         if (newton && !anyflip) break;
       }
     }
@@ -2661,15 +2411,6 @@ template <typename T, typename TS, int G> MJB_DEV void sensors(const Ctx<T>& c, 
 // ---------------------------------------------------------------------------
 // The three stages of mj_forward, separately callable: mjd_transitionFD skips the stages a perturbed column cannot change
 // (MuJoCo's mj_stepSkip: ctrl columns keep the position and velocity stages, velocity columns the position stage).
-// Diagnostic build -DMJB_PHASE_REPEAT (scripts/gpu_phase_pmc.py): the phase whose index equals StepArgs::repeat_phase runs TWICE.
-// Every phase wrapped below recomputes its outputs from LDS inputs it does not modify (idempotent), so the state evolves exactly
-// as in the product kernel and the DIFFERENCE of the hardware counters of two passes (repeat k vs no repeat) is phase k's own
-// instruction count, active-lane cycles and executed flops.  The product build compiles the plain call.
-#if defined(MJB_PHASE_REPEAT) && !defined(MJB_HOST_EMU)
-#define MJB_PHASE_CALL(c, k, call) do { call; if ((c).rep == (k)) { gsync<G>(); call; } } while (0)
-#else
-#define MJB_PHASE_CALL(c, k, call) do { call; } while (0)
-#endif
 template <typename T, int G> MJB_DEV void forward_position(Ctx<T>& c) {
   MJB_STAMP(c, PH_OTHER);
   MJB_PHASE_CALL(c, PH_KIN, (kinematics<T, G>(c))); MJB_STAMP(c, PH_KIN);
@@ -2715,14 +2456,12 @@ template <typename T, int G> MJB_DEV void euler(Ctx<T>& c, const mjb_f16v* inv =
   T h = m.timestep;
   if (m.has_damping) {
     T *qs = w + L.qfrc_smooth, *qc = w + L.qfrc_constraint;
-#if defined(MJB_PHASE_REPEAT) && !defined(MJB_HOST_EMU)
-    if (c.rep == PH_INTEG) {                                   // the implicit-damping solve twice (right-hand side rebuilt: idempotent)
+    if (MJB_REPEATS(c, PH_INTEG)) {                            // the implicit-damping solve twice (right-hand side rebuilt: idempotent)
       for (int i = lane; i < nv; i += G) tmpv[i] = qs[i] + qc[i];
       gsync<G>();
       factor_W<T, G>(c, 2, tmpv);
       gsync<G>();
     }
-#endif
     for (int i = lane; i < nv; i += G) tmpv[i] = qs[i] + qc[i];
     gsync<G>();
 #ifndef MJB_HOST_EMU
@@ -3034,7 +2773,6 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
   double time;
   bool staged_in = false;
 #ifndef MJB_HOST_EMU
-#ifndef MJB_NO_XFER
   if constexpr (sizeof(T) == 4 && sizeof(TS) == 4) {
     if (tag_in != 0) {
       staged_in = true;
@@ -3077,7 +2815,6 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
     }
   }
 #endif
-#endif
   if (!staged_in) {
     for (int i = lane; i < nq; i += G) w[L.qpos + i] = (T)d.qpos[(size_t)env * nq + i];
     for (int i = lane; i < nv; i += G) {
@@ -3094,38 +2831,23 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
 #endif
   int badqpos = 0, badqvel = 0, badqacc = 0;
   gsync<G>();
-#if defined(MJB_PROFILE) && !defined(MJB_HOST_EMU)
-  c.pt = __builtin_amdgcn_s_memtime();
-#endif
+  MJB_STAMP_START(c);
   if (a.mode != 0) { s_begin = 0; s_end = 1; }
   c.skip_dynamics = a.mode == 2;
-#if defined(MJB_PHASE_REPEAT) && !defined(MJB_HOST_EMU)
-  c.rep = a.mode == 0 ? a.repeat_phase : -1;
-#endif
+  MJB_SET_REPEAT(c, a.mode == 0 ? a.repeat_phase : -1);
   const int nstage = (a.mode == 0 && m.integrator == INT_RK4) ? 4 : 1;
 #ifndef MJB_HOST_EMU
   const unsigned hwslot = __builtin_amdgcn_s_getreg((3 << 11) | 4);      // HW_ID[3:0]: this wave's slot on its SIMD
 #endif
   for (int s = s_begin; s < s_end; s++) {
-#if !defined(MJB_HOST_EMU) && defined(MJB_LANE_LAUNDER)
-    // Experiment (off; MJB_SPEC_FLAGS=-DMJB_LANE_LAUNDER): the lane index made opaque once per step, so that the lane-derived loop invariants
-    // of the pipeline (`lane < n` predicates, 64-bit table addresses of the baked model) are recomputed where they are used instead of being
-    // hoisted in front of the step loop and spilled there.  VGPR spills 77 -> 43, scratch instructions 132 -> 73, but 2.4 % SLOWER (41.8 vs
-    // 42.8 M env-steps/s): reloading a hoisted value costs less issue than recomputing it.  Bitwise identical either way.
-    MJB_OPAQUE1(lane);
-    __builtin_assume(lane >= 0 && lane < G);
-    c.lane = lane;
-#endif
 #ifndef MJB_HOST_EMU
     // Issue priority of the SIMD's co-resident waves: the hardware arbitrates VALU issue by priority, then AGE, so of two waves that
     // start together the older one runs ~10 % faster for its whole life and the launch waits for the younger (profiles/r02_wave_timeline.log).
     // Bit `fair_bit` of the 100 MHz wall clock, which all waves read alike, hands the priority back and forth between odd and even slots.
-#ifndef MJB_NO_FAIR
     if (a.fair_bit > 0) {
       const unsigned ph = (unsigned)(__builtin_amdgcn_s_memrealtime() >> (unsigned)a.fair_bit);
       if ((ph + hwslot) & 1u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
     }
-#endif
 #endif
     if (a.mode == 0) {
       if (group_bad<T, G>(w + L.qpos, nq, lane)) { badqpos++; reset_state<T, G>(c); time = 0; }
@@ -3149,18 +2871,14 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
     if (a.mode != 0) break;
     if (nstage == 1) euler<T, G>(c);
     MJB_STAMP(c, PH_INTEG);
-#if defined(MJB_TIMELINE) && !defined(MJB_HOST_EMU)
     if (tlacc) *tlacc += ((unsigned long long)(unsigned)c.niter << 8) | ((unsigned long long)(unsigned)c.nefc << 24) | ((unsigned long long)(unsigned)c.ncon << 44);
-#endif
     time += a.dt;
     if (a.obs_every > 0 && ((s + 1) % a.obs_every) == 0) {
       size_t slot = (size_t)((s + 1) / a.obs_every - 1);
       write_obs<T, TS, G>(c, obs, time, obs_out + (slot * (size_t)d.batch + (size_t)env) * (size_t)obs.dim);
     }
   }
-#if defined(MJB_PROFILE) && !defined(MJB_HOST_EMU)
-  if (lane == 0 && d.prof) for (int k = 0; k < PH_N; k++) atomicAdd(d.prof + k, c.pacc[k]);
-#endif
+  MJB_PROF_FLUSH(c, d.prof, lane);
   // the accumulating counters are almost always zero: device-scope atomics only when there is something to add
   if (lane == 0) {
     int* cn = d.counters + (size_t)env * CNT_N;
@@ -3177,7 +2895,7 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
     cn[CNT_BADQPOS] += badqpos; cn[CNT_BADQVEL] += badqvel; cn[CNT_BADQACC] += badqacc;
 #endif
   }
-#if !defined(MJB_HOST_EMU) && !defined(MJB_NO_XFER)
+#ifndef MJB_HOST_EMU
   if constexpr (sizeof(T) == 4 && sizeof(TS) == 4) {
     // the hand-over made at step s_end carries tag tagbase + s_end
     unsigned tag_out = (a.mode == 0 && a.chunk_steps > 0 && s_end < a.nstep) ? a.tagbase + (unsigned)s_end : 0u;

@@ -56,11 +56,7 @@ MJB_DEV void k_step_body() {
     MJB_SPEC_ASSUME_LAY(L)
     T* w = (T*)(smem + (size_t)sub * L.bytes);
     int* wi = (int*)(w + L.nT);
-#ifdef MJB_NO_TICKETS                      // experiment: what does the ticket loop cost the static map?
-    const bool tickets = false;
-#else
     const bool tickets = a.chunk_steps > 0 && a.mode == 0;
-#endif
     unsigned blk = blockIdx.x;
     int s0 = 0, s1 = a.nstep;
     unsigned tag_in = 0;
@@ -78,11 +74,7 @@ MJB_DEV void k_step_body() {
     const int env = (int)blk * (64 / G) + sub;
     if (env < d.batch) env_run<T, TS, G>(mp, lp, d, kp->dbg, a, kp->obs, kp->obs_out, w, wi, env, lane, s0, s1, tag_in, MJB_TLACC);
     asm volatile("" : "+s"(kp));                              // (not even the map's flag is carried across env_run)
-#ifdef MJB_NO_TICKETS
-    break;
-#else
     if (!(kp->a.chunk_steps > 0 && kp->a.mode == 0)) break;
-#endif
 #if defined(MJB_TIMELINE)
     tlt++;
 #endif

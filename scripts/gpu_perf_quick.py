@@ -3,7 +3,7 @@ extra compile flags for the per-model specialised kernels, MJB_SPEC_FLAGS) the h
 20-step launches) and at B = 512 / 1024 (the small-batch kernel), best and median of 7 launches, plus a checksum of the final state
 (variants that only change code generation must agree bit for bit).
 
-    python scripts/gpu_perf_quick.py "" "-DMJB_NO_MASK_OPAQUE" ...
+    python scripts/gpu_perf_quick.py "" "-DMJB_WPS=1" ...
 """
 import os, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,6 @@
-// Micro-benchmark of mjb::mfma_factor32 (the fp32 MFMA Cholesky of the step kernel) in isolation:
-// cycles per call (s_memtime) for mode 0 (factor + solve) and mode 1 (Hessian assembly + factor + solve),
-// at 1 wave per CU and at 2 waves per SIMD.  Ablation knobs: -DMJB_MICRO_NOMFMA / NOSTORE / NONR / NOFWD.
+// Micro-benchmark of the fp32 MFMA solves of the step kernel in isolation: mjb::mfma_sweep_solve32 (the sweep inverse), or
+// with -DMICRO_CHOL mjb::mfma_factor32 (the Cholesky the Hessian keeps).  Cycles per call (s_memtime) for mode 0 (factor + solve)
+// and mode 1 (Hessian assembly + factor + solve), at 1 wave per CU and at 2 waves per SIMD.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -9,7 +9,7 @@
 struct MiniRef { float timestep; const float* dof_damping; };
 __global__ __launch_bounds__(64, 2) void kb(int n, int nefc, int mode, int iters, const float* Min, const float* Jin, const float* dwin, float* xout, unsigned long long* cyc, int pad_lds) {
   extern __shared__ float lds[];
-  float *M = lds, *W = M + n * n, *dinv = W + 528, *J = dinv + 40, *dw = J + 64 * n, *x = dw + 64;
+  float *M = lds, *W = M + n * n, *dinv = W + 528, *J = dinv + 40, *dw = J + 64 * n, *x = dw + 64, *ybuf = x + 32;
   int lane = threadIdx.x;
   for (int i = lane; i < n * n; i += 64) M[i] = Min[i];
   for (int i = lane; i < nefc * n; i += 64) J[i] = Jin[i];
@@ -22,7 +22,7 @@ __global__ __launch_bounds__(64, 2) void kb(int n, int nefc, int mode, int iters
     if (lane < n) x[lane] = 1.0f + 0.01f * lane;
     __syncthreads();
 #ifdef MICRO_CHOL
-    mjb::mfma_factor32<MiniRef>(m, M, W, dinv, J, dw, nefc, mode, n, lane, x, pf);
+    mjb::mfma_factor32<MiniRef>(m, M, W, dinv, ybuf, J, dw, nefc, mode, n, lane, x, pf);
 #else
     mjb::mfma_sweep_solve32<MiniRef>(m, M, dinv, J, dw, nefc, mode, n, lane, x, pf);
 #endif
