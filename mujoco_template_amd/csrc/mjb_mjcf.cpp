@@ -89,6 +89,8 @@ static std::string dir_of(const std::string& path) {
 
 // MuJoCo rejects a file that is included twice; here a repeat (which also covers self-inclusion and cycles) raises MjcfError
 // instead of recursing until the stack overflows.  `seen` holds the paths of every file included so far, canonicalised.
+// `depth` counts nested <include> files only; ordinary child elements keep their parent's depth, so a deep body tree
+// (a long serial chain) is not mistaken for runaway inclusion.
 static std::string canonical_path(const std::string& path) {
   char buf[PATH_MAX];
   return realpath(path.c_str(), buf) ? std::string(buf) : path;
@@ -106,7 +108,7 @@ static void expand_includes(Elem& e, const std::string& base_dir, std::set<std::
       expand_includes(*sub, dir_of(path), seen, depth + 1);
       for (auto& k : sub->kids) out.push_back(std::move(k));
     } else {
-      expand_includes(*c, base_dir, seen, depth + 1);
+      expand_includes(*c, base_dir, seen, depth);
       out.push_back(std::move(c));
     }
   }

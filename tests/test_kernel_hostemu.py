@@ -243,3 +243,74 @@ def test_fp32_joint_angles_beyond_pi_on_the_cpu(compiled):
         od.qpos[:] = t32; od.qvel[:] = 0; od.forward()
         e.qpos[:] = t32; e.qvel[:] = 0; e.forward()
         assert np.abs(e.site_xpos.ravel() - od.site_xpos.ravel()).max() <= 2e-6 + 0.5 * 1.2e-7 * abs(theta), theta
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 33..64 dofs (tests/large_models.py): the register-tiled Cholesky on the 8x8 lane grid (tile_factor) and chol_solve for M, the
+# Newton Hessian and M + h diag(damping), the unsplit J^T f, and 64-bit dof masks filled up to bit 63.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _large(name, use_double, ncon_max=32, nefc_max=128):
+    from mujoco_template_amd import mjcf
+    from tests.large_models import LARGE_MODELS, initial_state
+    cm = mjcf.compile_xml_string(LARGE_MODELS[name]())
+    od = mjo.OracleData(mjo.OracleModel(cm))
+    q, v = initial_state(cm, name, np.random.default_rng(cm.nv))
+    od.qpos[:] = q; od.qvel[:] = v
+    return cm, od, EmuEnv(cm, G=64, use_double=use_double, ncon_max=ncon_max, nefc_max=nefc_max)
+
+
+def _rel(a, b):
+    return float(np.abs(a[:b.size] - b).max() / max(1.0, float(np.abs(b).max()))) if b.size else 0.0
+
+
+LARGE_NAMES = ["chain33", "chain40", "chain57", "chain64", "tree", "two_free"]
+
+
+@pytest.mark.parametrize("name", LARGE_NAMES)
+def test_large_nv_float64_forward_and_steps_match_oracle(name):
+    """float64 instantiation at nv = 33..64: forward phases (mass matrix, bias, constraint rows, qacc through the tiled Cholesky of the
+    Hessian) and 20 free-running steps under random control, against the oracle at <= 1e-9 relative, counters equal at every step."""
+    cm, od, e = _large(name, True)
+    assert 33 <= cm.nv <= 64
+    e.qpos[:] = od.qpos; e.qvel[:] = od.qvel
+    od.forward(); e.forward()
+    nefc = od.counters()["nefc"]
+    assert e.counters[1] == nefc >= 8                                    # the Newton Hessian (mode 1) is factored
+    for k in ("xpos", "cdof", "qM", "qfrc_bias", "qfrc_passive", "qfrc_actuator", "qacc_smooth", "qfrc_constraint", "qacc"):
+        assert _rel(getattr(e, k), getattr(od, k)) <= 1e-10, k
+    assert _rel(e.efc_J[: nefc * cm.nv], od.efc_J) <= 1e-10
+    assert _rel(e.efc_aref[:nefc], od.efc_aref) <= 1e-9 and _rel(e.efc_D[:nefc], od.efc_D) <= 1e-10
+    types = set()
+    for s in range(20):
+        u = od.random_ctrl(3, 0, s, 1.0)
+        od.ctrl[:] = u; e.ctrl[:cm.nu] = u
+        od.step(); e.step()
+        c = od.counters()
+        assert (e.counters[0], e.counters[1], e.counters[2]) == (c["ncon"], c["nefc"], c["solver_niter"]), s
+        assert e.counters[3] == 0 and e.counters[4] == 0                 # nothing dropped
+        types.update(od.efc_type().tolist())
+    assert _rel(e.qpos, od.qpos) <= 1e-9 and _rel(e.qvel, od.qvel) <= 1e-9
+    if name == "tree":
+        assert 1 in types                                                # the fixed tendon's limit row (EFC_LIMIT_TENDON) was active
+
+
+@pytest.mark.parametrize("name", LARGE_NAMES)
+def test_large_nv_fp32_teacher_forced_steps_on_the_cpu(name):
+    """fp32 instantiation at nv = 33..64, teacher-forced along the oracle's trajectory: qacc of the Newton solve (relative) and the
+    one-step qpos / qvel errors stay at the fp32 level."""
+    cm, od, e = _large(name, False)
+    worst_a = worst_q = worst_v = 0.0
+    rows = 0
+    for s in range(3):
+        u = od.random_ctrl(4, 0, s, 1.0)
+        e.qpos[:] = od.qpos; e.qvel[:] = od.qvel; e.qacc_warmstart[:] = od.qacc_warmstart; e.ctrl[:cm.nu] = u
+        od.ctrl[:] = u
+        od.forward(); e.forward()
+        assert e.counters[1] == od.counters()["nefc"]
+        rows = max(rows, int(e.counters[1]))
+        worst_a = max(worst_a, _rel(e.qacc, od.qacc), _rel(e.qacc_smooth, od.qacc_smooth))
+        od.step(); e.step()
+        worst_q = max(worst_q, float(np.abs(e.qpos - od.qpos).max()))
+        worst_v = max(worst_v, float((np.abs(e.qvel - od.qvel) / np.maximum(1.0, np.abs(od.qvel))).max()))
+    assert rows >= 8                                                     # the Hessian path was taken
+    assert worst_a < 5e-4 and worst_q < 2e-7 and worst_v < 5e-5          # measured 1.3e-4 / 6.9e-8 / 1.4e-5 (chain64)

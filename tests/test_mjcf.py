@@ -352,3 +352,55 @@ def test_model_load_xml_through_the_c_abi(models, tmp_path):
     assert L.mjb_model_load_xml_string(b"<mujoco><worldbody><body><joint/></body>", b".", ctypes.byref(m)) == -2 and b"XML parse error" in L.mjb_last_error()
     assert L.mjb_model_load_xml_string(b"<mujoco><worldbody><body><joint/></body></worldbody></mujoco>", b".", ctypes.byref(m)) == -2
     assert b"zero mass" in L.mjb_last_error()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Nesting depth: only <include> files count towards the 64-level guard, not nested bodies (a serial chain of 62+ links is
+# nested deeper than 64 XML elements and must compile).
+# ------------------------------------------------------------------------------------------------------------------------------
+def test_a_chain_of_100_nested_bodies_compiles():
+    n = 100
+    s = ["<mujoco><worldbody>"]
+    for k in range(n):
+        jt = "<joint type='hinge' axis='0 1 0'/>" if k % 2 == 0 else ""       # 50 dofs: nv stays <= 64
+        s.append(f"<body name='b{k}' pos='0.1 0 0'>{jt}<geom type='sphere' size='0.02'/>")
+    s.append("</body>" * n + "</worldbody></mujoco>")
+    cm = mjcf.compile_xml_string("".join(s))
+    assert cm.nbody == n + 1 and cm.nv == n // 2
+    assert list(cm.body_parentid) == [0] + list(range(n))
+    assert list(cm.body_depth) == list(range(n + 1))
+
+
+def test_a_64_dof_serial_chain_compiles():
+    from tests.large_models import chain_xml, two_free_xml
+    cm = mjcf.compile_xml_string(chain_xml(64))
+    assert cm.nv == cm.nq == 64 and cm.nbody == 65 and max(cm.body_depth) == 64
+    assert list(cm.dof_parentid) == [-1] + list(range(63))
+    cm = mjcf.compile_xml_string(two_free_xml())
+    assert cm.nv == 64 and cm.nq == 66 and list(cm.jnt_type)[-1] == 0 and list(cm.jnt_dofadr)[-1] == 58     # dof 63: the box's free joint
+
+
+def _include_chain(tmp_path, levels):
+    """main.xml includes inc1.xml, which includes inc2.xml, ... down to inc<levels>.xml, which holds the body."""
+    for k in range(1, levels):
+        (tmp_path / f"inc{k}.xml").write_text(f"<mujoco><include file='inc{k + 1}.xml'/></mujoco>")
+    (tmp_path / f"inc{levels}.xml").write_text("<mujoco><worldbody><body><joint type='hinge'/><geom size='0.1'/></body></worldbody></mujoco>")
+    (tmp_path / "main.xml").write_text("<mujoco><include file='inc1.xml'/></mujoco>")
+    return str(tmp_path / "main.xml")
+
+
+def test_include_nesting_is_limited_to_64_levels(tmp_path):
+    (tmp_path / "ok").mkdir(); (tmp_path / "deep").mkdir()
+    assert mjcf.compile_xml_path(_include_chain(tmp_path / "ok", 64)).nv == 1
+    with pytest.raises(mjcf.MjcfError, match="nesting deeper than 64"):
+        mjcf.compile_xml_path(_include_chain(tmp_path / "deep", 65))
+
+
+def test_include_cycles_and_self_inclusion_are_rejected(tmp_path):
+    (tmp_path / "self.xml").write_text("<mujoco><include file='self.xml'/></mujoco>")
+    with pytest.raises(mjcf.MjcfError, match="include cycle"):
+        mjcf.compile_xml_path(str(tmp_path / "self.xml"))
+    (tmp_path / "a.xml").write_text("<mujoco><include file='b.xml'/></mujoco>")
+    (tmp_path / "b.xml").write_text("<mujoco><worldbody><body><geom size='0.1'/></body></worldbody><include file='a.xml'/></mujoco>")
+    with pytest.raises(mjcf.MjcfError, match="include cycle"):
+        mjcf.compile_xml_path(str(tmp_path / "a.xml"))
