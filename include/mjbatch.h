@@ -139,29 +139,26 @@ int mjb_mirror_edited_mask(mjbData* d, int* mask_out);
 int mjb_mirror_commit(mjbData* d, int field_mask);
 int mjb_step_host_auto(mjbData* d, int nstep, int compare, int* mask_out);
 
-/* ---- per-model specialisation of the fp32 step kernel (no reference counterpart: the reference's MjModel is interpreted by
- * one pre-built C library; here the structural sizes of the compiled model and the LDS layout offsets can be folded into the
- * kernel).  mjb_model_spec_source / mjb_spec_source write the translation unit (returns its length; call with buf = NULL to
- * size it); compile it for gfx950 with `hipcc --genco -I <csrc>` (mujoco_template_amd/_capi.py does, cached in-tree) and hand
- * the code object to mjb_spec_load: every later launch on this data object uses it (same arguments, same results).
- * The generic kernel stays the default and the fallback. ---- */
-long mjb_model_spec_source(mjbModel* m, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap);
-long mjb_spec_source(mjbData* d, char* buf, long cap);
-int mjb_spec_load(mjbData* d, const void* code_object, long nbytes);
-int mjb_spec_unload(mjbData* d);
-/* The same for the TWO-WAVE step kernel that stepping launches use on small batches (one environment per 128-thread workgroup, the
- * independent phases of a step side by side on its two wavefronts; fp32, one wave per environment, nv <= 32, Euler): results bitwise
- * those of the one-wave kernel.  mjb_step_schedule()[5] tells whether a launch used it; MJB_TWO_WAVE=0 / 1 forces it off / on. */
-long mjb_model_step2_spec_source(mjbModel* m, int lanes, int nconmax, int nefcmax, char* buf, long cap);
-long mjb_step2_spec_source(mjbData* d, char* buf, long cap);
-int mjb_step2_spec_load(mjbData* d, const void* code_object, long nbytes);
-int mjb_step2_spec_unload(mjbData* d);
-/* The same for the float64 finite-difference kernel behind mjb_transition_fd (k_fd<double, TS, G> of this data object: float64 layout,
- * model baked in as float64 constants): source -> `hipcc --genco` -> mjb_fd_spec_load; results bitwise those of the generic kernel. */
-long mjb_model_fd_spec_source(mjbModel* m, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap);   /* without a data object (build step) */
-long mjb_fd_spec_source(mjbData* d, char* buf, long cap);
-int mjb_fd_spec_load(mjbData* d, const void* code_object, long nbytes);
-int mjb_fd_spec_unload(mjbData* d);
+/* ---- per-model specialised kernels (no reference counterpart: the reference's MjModel is interpreted by one pre-built C library;
+ * here the structural sizes of the compiled model and the LDS layout offsets can be folded into a kernel, and the model itself baked
+ * in as constants).  Three kinds, each with results bitwise those of the generic kernel it replaces:
+ *   MJB_KERNEL_STEP   the fp32 step kernel (float32 data objects only);
+ *   MJB_KERNEL_FD     the float64 finite-difference kernel behind mjb_transition_fd (k_fd<double, TS, G>: float64 layout);
+ *   MJB_KERNEL_STEP2  the TWO-WAVE step kernel that stepping launches use on small batches (one environment per 128-thread workgroup,
+ *                     the independent phases of a step side by side on its two wavefronts; fp32, one wave per environment,
+ *                     nv <= 32, Euler).  mjb_step_schedule()[5] tells whether a launch used it; MJB_TWO_WAVE=0 / 1 forces it off / on.
+ * mjb_kernel_source writes a data object's translation unit of that kind, mjb_model_kernel_source the one a data object created
+ * with these arguments would get (no device needed: a build step); both return its length (call with buf = NULL to size it) or -1
+ * where the kind does not apply or mjb_data_create would reject the arguments.  Compile it for gfx950 with
+ * `hipcc --genco -I <csrc>` (mujoco_template_amd/_capi.py does, cached in-tree) and hand the code object to mjb_kernel_load: every
+ * later launch of that kernel on this data object uses it.  The generic kernels stay the default and the fallback. ---- */
+#define MJB_KERNEL_STEP 1
+#define MJB_KERNEL_FD 2
+#define MJB_KERNEL_STEP2 3
+long mjb_model_kernel_source(mjbModel* m, int kind, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap);
+long mjb_kernel_source(mjbData* d, int kind, char* buf, long cap);
+int mjb_kernel_load(mjbData* d, int kind, const void* code_object, long nbytes);
+int mjb_kernel_unload(mjbData* d, int kind);
 
 /* mj_resetData / mj_resetDataKeyframe (reference model.py:59-71); key < 0 = qpos0 */
 int mjb_reset(mjbData* d, int key);

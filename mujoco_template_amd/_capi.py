@@ -23,6 +23,7 @@ _LIB_PATH = os.environ.get("MJB_LIB") or os.path.join(_HERE, "libmjbatch_prof.so
 _LIB: ctypes.CDLL | None = None
 
 MJB_F32, MJB_F64 = 0, 1
+MJB_KERNEL_STEP, MJB_KERNEL_FD, MJB_KERNEL_STEP2 = 1, 2, 3      # kinds of per-model specialised kernel
 CTRL_KEEP, CTRL_ZERO, CTRL_RANDOM, CTRL_FEEDBACK = 0, 1, 2, 3
 COUNTER_NAMES = ("ncon", "nefc", "solver_niter", "con_dropped", "efc_dropped", "warn_badqpos", "warn_badqvel", "warn_badqacc")
 
@@ -72,24 +73,12 @@ def load_library() -> ctypes.CDLL:
     L.mjb_reset_envs.argtypes = [vp, ci, vp, cu, cd, cd]
     L.mjb_forward_envs.argtypes = [vp, vp]
     L.mjb_engine_flags_peek.argtypes = [vp, pci]
-    L.mjb_model_spec_source.argtypes = [vp, ci, ci, ci, ci, ctypes.c_char_p, cl]
-    L.mjb_model_spec_source.restype = cl
-    L.mjb_spec_source.argtypes = [vp, ctypes.c_char_p, cl]
-    L.mjb_spec_source.restype = cl
-    L.mjb_spec_load.argtypes = [vp, ctypes.c_char_p, cl]
-    L.mjb_spec_unload.argtypes = [vp]
-    L.mjb_model_step2_spec_source.argtypes = [vp, ci, ci, ci, ctypes.c_char_p, cl]
-    L.mjb_model_step2_spec_source.restype = cl
-    L.mjb_step2_spec_source.argtypes = [vp, ctypes.c_char_p, cl]
-    L.mjb_step2_spec_source.restype = cl
-    L.mjb_step2_spec_load.argtypes = [vp, ctypes.c_char_p, cl]
-    L.mjb_step2_spec_unload.argtypes = [vp]
-    L.mjb_model_fd_spec_source.argtypes = [vp, ci, ci, ci, ci, ctypes.c_char_p, cl]
-    L.mjb_model_fd_spec_source.restype = cl
-    L.mjb_fd_spec_source.argtypes = [vp, ctypes.c_char_p, cl]
-    L.mjb_fd_spec_source.restype = cl
-    L.mjb_fd_spec_load.argtypes = [vp, ctypes.c_char_p, cl]
-    L.mjb_fd_spec_unload.argtypes = [vp]
+    L.mjb_model_kernel_source.argtypes = [vp, ci, ci, ci, ci, ci, ctypes.c_char_p, cl]
+    L.mjb_model_kernel_source.restype = cl
+    L.mjb_kernel_source.argtypes = [vp, ci, ctypes.c_char_p, cl]
+    L.mjb_kernel_source.restype = cl
+    L.mjb_kernel_load.argtypes = [vp, ci, ctypes.c_char_p, cl]
+    L.mjb_kernel_unload.argtypes = [vp, ci]
     L.mjb_inverse.argtypes = [vp]
     L.mjb_step.argtypes = [vp, ci]
     L.mjb_rollout.argtypes = [vp, ci, ci, cu, cu, cd, vp, vp, ci]
@@ -137,7 +126,7 @@ def load_library() -> ctypes.CDLL:
     L.mjb_step_host_auto.argtypes = [vp, ci, ci, ctypes.POINTER(ci)]
     for name in ("mjb_model_create", "mjb_model_set_disableactuator", "mjb_model_set_solver", "mjb_data_create", "mjb_set_stream",
                  "mjb_sync", "mjb_data_info", "mjb_array_ptr", "mjb_get_array", "mjb_set_array", "mjb_get_counters", "mjb_reset",
-                 "mjb_forward", "mjb_inverse", "mjb_spec_load", "mjb_spec_unload", "mjb_fd_spec_load", "mjb_fd_spec_unload", "mjb_step2_spec_load", "mjb_step2_spec_unload", "mjb_step", "mjb_rollout", "mjb_obs_spec_create", "mjb_obs_dim", "mjb_obs_gather",
+                 "mjb_forward", "mjb_inverse", "mjb_kernel_load", "mjb_kernel_unload", "mjb_step", "mjb_rollout", "mjb_obs_spec_create", "mjb_obs_dim", "mjb_obs_gather",
                  "mjb_transition_fd", "mjb_jac", "mjb_debug_forward", "mjb_debug_get", "mjb_model_field", "mjb_model_field_at", "mjb_model_save",
                  "mjb_model_load", "mjb_model_load_xml", "mjb_model_load_xml_string", "mjb_integrate_pos", "mjb_differentiate_pos", "mjb_host_view", "mjb_sync_to_host", "mjb_sync_to_device",
                  "mjb_step_host", "mjb_mirror_edited_mask", "mjb_mirror_commit", "mjb_step_host_auto", "mjb_engine_flags",
@@ -177,7 +166,7 @@ def _ids(seq: Sequence[int]):
 
 
 # ----------------------------------------------------------------------------------
-# per-model specialisation of the fp32 step kernel (include/mjbatch.h: mjb_*spec*)
+# per-model specialised kernels (include/mjbatch.h: mjb_*kernel_source, mjb_kernel_load)
 # ----------------------------------------------------------------------------------
 _WARNED_NO_SPEC = False
 _CSRC = os.path.join(_HERE, "csrc")
@@ -201,9 +190,6 @@ def spec_scheduler(source: str) -> str | None:
     with this flag was seen (ROCm 7.2.0 clang, greedy register allocator, ``profiles/r02_hipcc_iterative_ilp_crash.txt``)."""
     import re
 
-    forced = os.environ.get("MJB_SPEC_SCHED")                  # experiments: "iterative-ilp", "default", ...
-    if forced is not None:
-        return None if forced in ("", "default") else forced
     g = re.search(r"#define MJB_SPEC_G (\d+)", source)
     ne = re.search(r"nefc_max == (\d+)", source)
     lanes, rows = (int(g.group(1)) if g else 0), (int(ne.group(1)) if ne else 0)
@@ -244,7 +230,7 @@ def _read_private(path: str) -> bytes:
 
 
 def compile_spec(source: str, *, force: bool = False) -> str:
-    """Compile a specialised translation unit (``mjb_*spec_source``) to a gfx950 code object; returns its path.
+    """Compile a specialised translation unit (``mjb_*kernel_source``) to a gfx950 code object; returns its path.
 
     Cached in-tree (``mujoco_template_amd/_jit/``, keyed by the source text, the kernel headers and the scheduler rule), so
     the objects built by ``__graft_entry__.build()`` on a GPU-less machine travel with the tree; a read-only install uses a
@@ -423,20 +409,23 @@ class DeviceModel:
     def set_solver(self, iterations: int, tolerance: float) -> None:
         _check(load_library().mjb_model_set_solver(self.ptr, int(iterations), float(tolerance)))
 
+    def _model_source(self, kind: int, dtype: int, lanes: int, nconmax: int, nefcmax: int) -> str:
+        return _source_from(load_library().mjb_model_kernel_source, self.ptr, kind, dtype, int(lanes), int(nconmax), int(nefcmax))
+
     def spec_source(self, *, lanes: int = 0, nconmax: int = 0, nefcmax: int = 0) -> str:
         """Translation unit of the specialised fp32 step kernel for these creation arguments (no GPU needed)."""
-        return _source_from(load_library().mjb_model_spec_source, self.ptr, MJB_F32, int(lanes), int(nconmax), int(nefcmax))
+        return self._model_source(MJB_KERNEL_STEP, MJB_F32, lanes, nconmax, nefcmax)
 
     def step2_spec_source(self, *, lanes: int = 0, nconmax: int = 0, nefcmax: int = 0) -> str | None:
-        """Translation unit of the specialised two-wave step kernel (small batches), or None when that kernel does not apply to the model."""
+        """Translation unit of the specialised two-wave step kernel (small batches), or None when that kernel does not apply."""
         try:
-            return _source_from(load_library().mjb_model_step2_spec_source, self.ptr, int(lanes), int(nconmax), int(nefcmax))
+            return self._model_source(MJB_KERNEL_STEP2, MJB_F32, lanes, nconmax, nefcmax)
         except TemplateError:
             return None
 
     def fd_spec_source(self, *, dtype: str = "float32", lanes: int = 0, nconmax: int = 0, nefcmax: int = 0) -> str:
         """Translation unit of the specialised float64 finite-difference kernel for these creation arguments (no GPU needed)."""
-        return _source_from(load_library().mjb_model_fd_spec_source, self.ptr, MJB_F32 if dtype == "float32" else MJB_F64, int(lanes), int(nconmax), int(nefcmax))
+        return self._model_source(MJB_KERNEL_FD, MJB_F32 if dtype == "float32" else MJB_F64, lanes, nconmax, nefcmax)
 
     def __del__(self):
         try:
@@ -466,65 +455,69 @@ class BatchSim:
         info = [ctypes.c_int() for _ in range(6)]
         _check(L.mjb_data_info(self.ptr, *[ctypes.byref(x) for x in info]))
         self.lanes, self.nconmax, self.nefcmax, self.lds_bytes_per_env = info[2].value, info[3].value, info[4].value, info[5].value
-        # per-model specialised fp32 kernel: on by default (MJB_SPECIALIZE=0 turns the default off); an explicit True raises
-        # if it cannot be built, the default falls back to the generic kernel with one warning
         self.specialized = False
         self.fd_specialized = False
-        self._fd_spec_tried = False
+        self._fd_spec_tried = False                                 # the FD kernel is specialised by the first transition_fd
         self._spec_policy = specialize                             # None: default (on unless MJB_SPECIALIZE=0); True: required; False: never
-        want = specialize if specialize is not None else (dtype == "float32" and os.environ.get("MJB_SPECIALIZE", "1") != "0")
-        if want:
-            try:
-                self.specialize()
-            except TemplateError as exc:
-                if specialize:
-                    raise
-                global _WARNED_NO_SPEC
-                if not _WARNED_NO_SPEC:
-                    import warnings
+        self._specialize_by_policy(self.specialize, "step kernel", default=dtype == "float32", once_per_process=True)
 
-                    warnings.warn(f"step kernel not specialised, using the generic kernel: {exc}", RuntimeWarning, stacklevel=2)
-                    _WARNED_NO_SPEC = True
+    # -- per-model specialised kernels ------------------------------------------------
+    def _specialize_by_policy(self, specialize, what: str, *, default: bool, once_per_process: bool = False) -> None:
+        """Run ``specialize`` under the ``specialize=`` policy of this object: None = where ``default`` says so unless
+        MJB_SPECIALIZE=0, True = required (a failure raises), False = never.  A default that cannot be built falls back to the
+        generic kernel with one warning (per object, or per process with ``once_per_process``)."""
+        policy = self._spec_policy
+        if not (policy if policy is not None else default and os.environ.get("MJB_SPECIALIZE", "1") != "0"):
+            return
+        try:
+            specialize()
+        except TemplateError as exc:
+            if policy:
+                raise
+            global _WARNED_NO_SPEC
+            if once_per_process:
+                if _WARNED_NO_SPEC:
+                    return
+                _WARNED_NO_SPEC = True
+            import warnings
 
-    # -- per-model specialised kernel ------------------------------------------------
+            warnings.warn(f"{what} not specialised, using the generic kernel: {exc}", RuntimeWarning, stacklevel=3)
+
+    def _load_kernel(self, kind: int) -> None:
+        """This object's translation unit of ``kind`` -> code object (compiled, or from the cache) -> used by every later launch."""
+        image = _read_private(compile_spec(_source_from(load_library().mjb_kernel_source, self.ptr, kind)))
+        _check(load_library().mjb_kernel_load(self.ptr, kind, image, len(image)))
+
     def spec_source(self) -> str:
-        return _source_from(load_library().mjb_spec_source, self.ptr)
+        return _source_from(load_library().mjb_kernel_source, self.ptr, MJB_KERNEL_STEP)
 
     def specialize(self) -> None:
         """Compile (or fetch from the in-tree cache) the step kernel specialised to this model's sizes and LDS layout and
         use it for every later launch on this object.  float32 only; identical arithmetic to the generic kernel."""
         if self.dtype != "float32":
             raise ConfigError("only the float32 step kernel is specialised")
-        image = _read_private(compile_spec(self.spec_source()))
-        _check(load_library().mjb_spec_load(self.ptr, image, len(image)))
+        self._load_kernel(MJB_KERNEL_STEP)
         self.specialized = True
-        # small batches are stepped by the two-wave kernel where it applies: specialise that one too
-        if self.batch <= 1024:
-            try:
-                src2 = _source_from(load_library().mjb_step2_spec_source, self.ptr)
-            except TemplateError:
-                src2 = None
-            if src2 is not None:
-                image2 = _read_private(compile_spec(src2))
-                _check(load_library().mjb_step2_spec_load(self.ptr, image2, len(image2)))
+        # small batches are stepped by the two-wave kernel where it applies (its source length is -1 where not): specialise that one too
+        if self.batch <= 1024 and load_library().mjb_kernel_source(self.ptr, MJB_KERNEL_STEP2, None, 0) >= 0:
+            self._load_kernel(MJB_KERNEL_STEP2)
 
     def unspecialize(self) -> None:
-        _check(load_library().mjb_step2_spec_unload(self.ptr))
-        _check(load_library().mjb_spec_unload(self.ptr))
+        _check(load_library().mjb_kernel_unload(self.ptr, MJB_KERNEL_STEP2))
+        _check(load_library().mjb_kernel_unload(self.ptr, MJB_KERNEL_STEP))
         self.specialized = False
 
     def fd_spec_source(self) -> str:
-        return _source_from(load_library().mjb_fd_spec_source, self.ptr)
+        return _source_from(load_library().mjb_kernel_source, self.ptr, MJB_KERNEL_FD)
 
     def specialize_fd(self) -> None:
         """The float64 finite-difference kernel behind ``transition_fd`` specialised to this model (sizes, float64 LDS layout,
         the model baked in as constants); identical arithmetic to the generic kernel.  Done lazily by the first ``transition_fd``."""
-        image = _read_private(compile_spec(self.fd_spec_source()))
-        _check(load_library().mjb_fd_spec_load(self.ptr, image, len(image)))
+        self._load_kernel(MJB_KERNEL_FD)
         self.fd_specialized = True
 
     def unspecialize_fd(self) -> None:
-        _check(load_library().mjb_fd_spec_unload(self.ptr))
+        _check(load_library().mjb_kernel_unload(self.ptr, MJB_KERNEL_FD))
         self.fd_specialized = False
 
     # -- plumbing -----------------------------------------------------------------
@@ -731,16 +724,7 @@ class BatchSim:
         m = self.model.compiled
         if not self._fd_spec_tried:                                # first call: the per-model specialised kernel, by the same policy as the step kernel
             self._fd_spec_tried = True
-            want = self._spec_policy if self._spec_policy is not None else os.environ.get("MJB_SPECIALIZE", "1") != "0"
-            if want:
-                try:
-                    self.specialize_fd()
-                except TemplateError as exc:
-                    if self._spec_policy:
-                        raise
-                    import warnings
-
-                    warnings.warn(f"finite-difference kernel not specialised, using the generic kernel: {exc}", RuntimeWarning, stacklevel=2)
+            self._specialize_by_policy(self.specialize_fd, "finite-difference kernel", default=True)
         pa, pb = ctypes.POINTER(ctypes.c_double)(), ctypes.POINTER(ctypes.c_double)()
         _check(load_library().mjb_transition_fd_pinned(self.ptr, float(eps), int(bool(centered)), ctypes.byref(pa), ctypes.byref(pb)))
         A = np.ctypeslib.as_array(pa, shape=(self.batch, 2 * m.nv, 2 * m.nv))

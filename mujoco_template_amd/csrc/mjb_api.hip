@@ -66,22 +66,27 @@ struct mjbObsSpec {
   std::vector<void*> owned;
 };
 
+// Launch configuration of a data object (derive_config): lane-group widths, caps on contacts / constraint rows, LDS layouts
+struct Config {
+  int G, G_fd, ncon_max, nefc_max;        // G: lanes per environment of the step kernel; G_fd: of the float64 FD / Jacobian kernels
+  Lay Lf, Ld;                             // fp32 / float64 layouts of one environment's LDS slice
+  Lay Lf2;                                // flat fp32 layout of the two-wave step kernel (k_step2); bytes == 0: that kernel does not apply
+};
+
 struct mjbData {
   mjbModel* model;
-  int batch, dtype, G, G_fd, ncon_max, nefc_max, device, env0;
+  int batch, dtype, device, env0;
+  Config cfg;
   hipStream_t stream;
   DevAlloc alloc;
   DevModel<float> mf;
   DevModel<double> md;
-  Lay Lf, Ld;
-  DevModel<float>* mf_dev = nullptr;    // device copies of the structs above (read through the constant address space)
+  DevModel<float>* mf_dev = nullptr;    // device copies of the structs above and of the layouts (read through the constant address space)
   DevModel<double>* md_dev = nullptr;
-  Lay *Lf_dev = nullptr, *Ld_dev = nullptr;
-  Lay Lf2;                                  // flat fp32 layout of the two-wave step kernel (k_step2); bytes == 0: that kernel does not apply
-  Lay* Lf2_dev = nullptr;
-  hipModule_t spec2_mod = nullptr;          // per-model specialised two-wave kernel (mjb_step2_spec_load)
-  hipFunction_t spec2_fn = nullptr;
-  int ncu = 0;                              // CUs of the device (queried once)
+  Lay *Lf_dev = nullptr, *Ld_dev = nullptr, *Lf2_dev = nullptr;
+  // per-model specialised kernels (mjb_kernel_load), indexed by MJB_KERNEL_*; a null function = the generic kernel
+  struct { hipModule_t mod; hipFunction_t fn; } spec[4] = {};
+  int ncu = 0;                              // CUs of the device (queried once, by mjb_data_create)
   int two_wave = -1;                        // MJB_TWO_WAVE: 0 never, 1 whenever it applies, -1 (default) the policy in launch()
   int up_disable = -1, up_iter = -1; double up_tol = -1;
   DevData<float> df;
@@ -96,11 +101,6 @@ struct mjbData {
   // device-side feedback controller gains (float and double copies): K [nu, 2nv], u0 [nu], q0 [nq], v0 [nv]
   float* fbf[4] = {nullptr, nullptr, nullptr, nullptr};
   double* fbd[4] = {nullptr, nullptr, nullptr, nullptr};
-  // per-model specialised fp32 step kernel (mjb_spec_load); null = generic kernel
-  hipModule_t spec_mod = nullptr;
-  hipFunction_t spec_fn = nullptr;
-  hipModule_t fd_spec_mod = nullptr;       // per-model specialised float64 finite-difference kernel (mjb_fd_spec_load); null = generic k_fd
-  hipFunction_t fd_spec_fn = nullptr;
   // work scheduling of k_step (launch()): resident workgroups of the kernel in use on this device; < 0 = not yet queried
   long step_slots = -1;
   int sched_chunk = -1, fair_bit = -1;     // experiment overrides (MJB_CHUNK_STEPS, MJB_FAIR_BIT); -1 = policy below
@@ -239,7 +239,7 @@ template <typename TS> int alloc_state(mjbData* d, DevData<TS>& s) {
 
 template <typename TS> int alloc_debug(mjbData* d, DevDebug<TS>& g) {
   const HostModel& h = d->model->h;
-  size_t B = (size_t)d->batch, nv = h.nv, ne = d->nefc_max, nc = d->ncon_max;
+  size_t B = (size_t)d->batch, nv = h.nv, ne = d->cfg.nefc_max, nc = d->cfg.ncon_max;
   int rc = 0;
   rc |= dev_alloc(d, &g.qM, B * nv * nv); rc |= dev_alloc(d, &g.qfrc_bias, B * nv); rc |= dev_alloc(d, &g.qfrc_passive, B * nv);
   rc |= dev_alloc(d, &g.qfrc_actuator, B * nv); rc |= dev_alloc(d, &g.qacc_smooth, B * nv); rc |= dev_alloc(d, &g.qfrc_constraint, B * nv);
@@ -276,7 +276,10 @@ int refresh_options(mjbData* d) {
 }
 
 
-// Default caps on contacts / constraint rows held in LDS per environment (see mjb_data_create).
+// Caps on contacts / constraint rows held in LDS per environment.  Explicit values are taken as given.  Default: the model's own
+// worst case when that is small (<= 96 rows, <= 32 contacts); otherwise the largest (rows <= 96, contacts = 3/8 rows) that still
+// lets 8 fp32 (4 fp64) wavefronts share one CU's 160 KiB — the occupancy step that matters most for throughput (profiles/).
+// Overflow drops rows and is COUNTED.
 void choose_caps(const HostModel& h, int dtype, int lanes, int nconmax, int nefcmax, int& nc_out, int& ne_out) {
   int ne, nc;
   if (nconmax > 0 || nefcmax > 0) {
@@ -309,35 +312,81 @@ void choose_caps(const HostModel& h, int dtype, int lanes, int nconmax, int nefc
 }
 int auto_lanes(const HostModel& h, int lanes) { return lanes == 0 ? (h.nv <= 4 ? 8 : (h.nv <= 16 ? 16 : 64)) : lanes; }
 
+// The launch configuration of a data object of model h created with these arguments: mjb_data_create keeps it, and the model-level
+// kernel sources derive it here too, so a kernel built from the model alone is the one a data object later asks for.
+bool derive_config(const HostModel& h, int dtype, int lanes, int nconmax, int nefcmax, Config& c, std::string& err) {
+  c.G = auto_lanes(h, lanes);
+  if (c.G != 8 && c.G != 16 && c.G != 64) { err = "lanes must be 8, 16 or 64"; return false; }
+  choose_caps(h, dtype, c.G, nconmax, nefcmax, c.ncon_max, c.nefc_max);
+  c.Lf = make_layout(h, c.ncon_max, c.nefc_max, sizeof(float));
+  c.Ld = make_layout(h, c.ncon_max, c.nefc_max, sizeof(double));
+  // the float64 FD / Jacobian kernels may need more lanes per environment than the step kernel to fit LDS
+  c.G_fd = c.G;
+  while (c.G_fd < 64 && (size_t)(64 / c.G_fd) * (size_t)c.Ld.bytes > 160 * 1024) c.G_fd = c.G_fd == 8 ? 16 : 64;
+  const size_t lds = (size_t)(64 / c.G) * (size_t)(dtype == MJB_F32 ? c.Lf.bytes : c.Ld.bytes);
+  if (lds > 160 * 1024 || (size_t)(64 / c.G_fd) * (size_t)c.Ld.bytes > 160 * 1024) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "per-workgroup LDS %zu B exceeds 160 KiB (lower nconmax/nefcmax or use more lanes)", lds);
+    err = buf;
+    return false;
+  }
+  std::memset(&c.Lf2, 0, sizeof(Lay));
+  if (dtype == MJB_F32 && c.G == 64 && h.nv <= 32 && h.integrator != INT_RK4) {
+    c.Lf2 = make_layout(h, c.ncon_max, c.nefc_max, sizeof(float), true);
+    if ((size_t)c.Lf2.bytes > 64 * 1024) std::memset(&c.Lf2, 0, sizeof(Lay));       // (never for the models this path is for)
+  }
+  return true;
+}
+
+// The per-model specialised kernels, indexed by MJB_KERNEL_*: the kernel's symbol in its code object, the first line of its generated
+// source (it names the entry points of an earlier ABI: kept as it is, because the source text keys the in-tree cache of code objects),
+// and why it may not apply to a configuration
+struct KernelKind { const char* symbol; const char* banner; const char* not_applicable; };
+const KernelKind kKinds[4] = {
+    {nullptr, nullptr, nullptr},
+    {"mjb_k_step_spec", "// generated by mjb_model_spec_source(): size- and layout-specialised k_step<float, float, G> of ONE compiled model\n",
+     "only the float32 step kernel is specialised"},
+    {"mjb_k_fd_spec", "// generated by mjb_fd_spec_source(): size- and layout-specialised k_fd<double, TS, G> of ONE compiled model\n", ""},
+    {"mjb_k_step2_spec", "// generated by mjb_step2_spec_source(): size- and (flat) layout-specialised two-wave step kernel k_step2<float, float> of ONE compiled model\n",
+     "the two-wave step kernel does not apply to this configuration (fp32, one wave per environment, nv <= 32, Euler)"},
+};
+bool valid_kind(int kind) { return kind == MJB_KERNEL_STEP || kind == MJB_KERNEL_FD || kind == MJB_KERNEL_STEP2; }
+
+// What a kernel kind is built for under configuration c: its LDS layout, lanes per environment, the state type TS of the data object
+struct KernelTarget { const Lay* L; int G; const char* ts; bool applies; };
+KernelTarget kernel_target(const Config& c, int dtype, int kind) {
+  switch (kind) {
+    case MJB_KERNEL_STEP: return {&c.Lf, c.G, "float", dtype == MJB_F32};
+    case MJB_KERNEL_FD: return {&c.Ld, c.G_fd, dtype == MJB_F32 ? "float" : "double", true};
+    default: return {&c.Lf2, 64, "float", c.Lf2.bytes > 0};                              // MJB_KERNEL_STEP2
+  }
+}
+int check_kind(const Config& c, int dtype, int kind) {
+  if (!valid_kind(kind)) return fail(MJB_ERR_ARG, "unknown kernel kind (MJB_KERNEL_STEP, MJB_KERNEL_FD or MJB_KERNEL_STEP2)");
+  if (!kernel_target(c, dtype, kind).applies) return fail(MJB_ERR_ARG, kKinds[kind].not_applicable);
+  return MJB_OK;
+}
+
 // The model itself as `__constant__` data of the specialised translation unit (MJB_SPEC_BAKED, mjb_device.hpp): fill_dev_model runs
 // against an allocator that EMITS every table as a C array and hands out recognisable tokens instead of addresses; the filled
 // DevModel<float> is then written out word by word as a struct of the same layout (pointer words -> the emitted arrays, everything
 // else -> the bit pattern), so the image cannot fall out of step with fill_dev_model or with the struct's member list.
 struct EmitAlloc {
-  // Two forms.  as_struct = false (default): one `static const __constant__` array per table - its own symbol, so a lane-indexed read
-  // is global_load(table address + lane offset) with no further address arithmetic.  as_struct = true (MJB_SPEC_BAKE=struct): every
-  // table a member of ONE struct - a single base address, an extra address add per lane-indexed read, far fewer address registers.
-  // Measured (scripts/gpu_spec_check.py, same box, B = 4096, M env-steps/s; pointer hops / struct / arrays): humanoid 41.7 / 43.1 /
-  // 43.4, drone2 178 / 193 / 218, cart-pole 215 / 230 / 248.  The humanoid kernel (256 VGPRs) spills 61 VGPRs to scratch with the
-  // array form (spill stores around the ticket loop, ~7 KB per environment and chunk switch: HBM write traffic 0.15 -> 1.2 GB per
-  // 1000-step launch) and far fewer with the struct form; it is still 2 % faster with the arrays (4 % on the two-wave kernel).
-  bool as_struct = false;
-  std::string text, decl, init;
+  // One `static const __constant__` array per table - its own symbol, so a lane-indexed read is global_load(table address + lane
+  // offset) with no further address arithmetic.  Measured (scripts/gpu_spec_check.py, same box, B = 4096, M env-steps/s; pointer
+  // hops / one struct of all tables / arrays): humanoid 41.7 / 43.1 / 43.4, drone2 178 / 193 / 218, cart-pole 215 / 230 / 248.  The
+  // humanoid kernel (256 VGPRs) spills 61 VGPRs to scratch with the array form (spill stores around the ticket loop, ~7 KB per
+  // environment and chunk switch: HBM write traffic 0.15 -> 1.2 GB per 1000-step launch) and far fewer with the struct form; it is
+  // still 2 % faster with the arrays (4 % on the two-wave kernel).  The struct form is at commit a705124.
+  std::string text;
   int n = 0;
   static constexpr unsigned long long TOKEN = 0x7E57AB1Eull << 32;
   template <typename X, typename F> const X* emit(const std::vector<X>& v, const char* ctype, F fmt) {
     std::string body;
     if (v.empty()) body = "0";
     for (size_t i = 0; i < v.size(); i++) { if (i) body += (i % 16 == 0 ? ",\n " : ","); body += fmt(v[i]); }
-    if (as_struct) {
-      decl += std::string("  ") + ctype + " t" + std::to_string(n) + "[" + std::to_string(v.empty() ? 1 : v.size()) + "];\n";
-      init += "  {" + body + "},\n";
-    } else text += std::string("static const __constant__ ") + ctype + " mjb_tab_" + std::to_string(n) + "[] = {" + body + "};\n";
+    text += std::string("static const __constant__ ") + ctype + " mjb_tab_" + std::to_string(n) + "[] = {" + body + "};\n";
     return (const X*)(uintptr_t)(TOKEN + (unsigned long long)(n++) * 16ull + 16ull);
-  }
-  std::string table_name(int k) const { return (as_struct ? "mjb_tabs.t" : "mjb_tab_") + std::to_string(k); }
-  std::string tables_source() const {
-    return as_struct ? "struct MjbBakedTables {\n" + decl + "};\nstatic const __constant__ MjbBakedTables mjb_tabs = {\n" + init + "};\n" : text;
   }
   const float* putf(const std::vector<float>& v) {
     return emit(v, "float", [](float x) {
@@ -360,11 +409,10 @@ struct EmitAlloc {
 };
 
 template <typename T>
-std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max, bool as_struct) {
+std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max) {
   static_assert(sizeof(DevModel<T>) % 8 == 0, "DevModel<T> is written out in 8-byte words");
   const char* tname = sizeof(T) == 4 ? "float" : "double";
   EmitAlloc ea;
-  ea.as_struct = as_struct;
   DevModel<T> m;
   fill_dev_model<T>(h, ea, ncon_max, nefc_max, m);
   const size_t nw = sizeof(m) / 8;
@@ -375,7 +423,7 @@ std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max, b
     const unsigned long long v = wv[i];
     if ((v >> 32) == (EmitAlloc::TOKEN >> 32)) {
       decl += " const void MJB_CONST* p" + std::to_string(i) + ";";
-      init += " (const void MJB_CONST*)" + ea.table_name((int)((v - EmitAlloc::TOKEN) / 16 - 1)) + ",";
+      init += " (const void MJB_CONST*)mjb_tab_" + std::to_string((int)((v - EmitAlloc::TOKEN) / 16 - 1)) + ",";
     } else {
       char b[64];
       decl += " unsigned a" + std::to_string(i) + ", b" + std::to_string(i) + ";";
@@ -399,20 +447,21 @@ std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max, b
     if (!ok) return std::string("// (model not baked in: the DevModel image did not map one-to-one onto the emitted tables)\n");
   }
   std::string s = "#include \"mjb_types.hpp\"\n// the model as constant data of this translation unit (tables, then the DevModel image)\n";
-  s += ea.tables_source() + decl + init;
+  s += ea.text + decl + init;
   s += std::string("static_assert(sizeof(MjbBakedModel) == sizeof(mjb::DevModel<") + tname + ">), \"baked model image\");\n";
   s += std::string("#define MJB_SPEC_BAKED (*(const mjb::DevModel<") + tname + "> MJB_CONST*)&mjb_baked_model)\n";
   return s;
 }
 
-// Translation unit of the specialised fp32 step kernel of one compiled model: the structural sizes of DevModel (never the
-// run-time options: disableactuator, iterations, tolerance) and every LDS layout offset become __builtin_assume()s.
-// kind 1: the fp32 step kernel (L = the fp32 layout); kind 2: the float64 finite-difference kernel k_fd<double, ts, G> (L = the float64 layout)
-std::string spec_source(const HostModel& h, const Lay& L, int G, int ncon_max, int nefc_max, int kind = 1, const char* ts = "float") {
-  std::string s = kind == 1 ? "// generated by mjb_model_spec_source(): size- and layout-specialised k_step<float, float, G> of ONE compiled model\n"
-                : kind == 2 ? "// generated by mjb_fd_spec_source(): size- and layout-specialised k_fd<double, TS, G> of ONE compiled model\n"
-                            : "// generated by mjb_step2_spec_source(): size- and (flat) layout-specialised two-wave step kernel k_step2<float, float> of ONE compiled model\n";
-  s += "#define MJB_SPEC_KERNEL " + std::to_string(kind) + "\n#define MJB_SPEC_TS " + ts + "\n#define MJB_SPEC_G " + std::to_string(G) + "\n#define MJB_SPEC_ASSUME(m)";
+// Translation unit of a per-model specialised kernel (kind: MJB_KERNEL_*) under configuration c: the structural sizes of DevModel
+// (never the run-time options: disableactuator, iterations, tolerance) and every offset of the kernel's LDS layout become
+// __builtin_assume()s, and the model itself becomes constant data of the translation unit.
+std::string spec_source(const HostModel& h, const Config& c, int dtype, int kind) {
+  const KernelTarget t = kernel_target(c, dtype, kind);
+  const Lay& L = *t.L;
+  const int ncon_max = c.ncon_max, nefc_max = c.nefc_max;
+  std::string s = kKinds[kind].banner;
+  s += "#define MJB_SPEC_KERNEL " + std::to_string(kind) + "\n#define MJB_SPEC_TS " + t.ts + "\n#define MJB_SPEC_G " + std::to_string(t.G) + "\n#define MJB_SPEC_ASSUME(m)";
   auto A = [&](const char* obj, const char* f, long v) { s += std::string(" __builtin_assume((") + obj + ")." + f + " == " + std::to_string(v) + ");"; };
 #define SM(f, v) A("m", #f, (long)(v))
   SM(nq, h.nq); SM(nv, h.nv); SM(nu, h.nu); SM(nbody, h.nbody); SM(njnt, h.njnt); SM(ngeom, h.ngeom); SM(nsite, h.nsite);
@@ -441,12 +490,7 @@ std::string spec_source(const HostModel& h, const Lay& L, int G, int ncon_max, i
     }
     if (le2) s += "#define MJB_SPEC_SOLIMP_POWER_1_OR_2 1\n";       // (model fields are read-only after compilation: only the solver options change at run time)
   }
-  {
-    const char* e = std::getenv("MJB_SPEC_BAKE");                 // experiments: "off", "struct", "arrays"
-    const std::string mode = e ? e : "arrays";
-    if (mode != "off" && !std::getenv("MJB_SPEC_NO_BAKE"))
-      s += kind != 2 ? baked_model_source<float>(h, ncon_max, nefc_max, mode == "struct") : baked_model_source<double>(h, ncon_max, nefc_max, mode == "struct");
-  }
+  s += kind != MJB_KERNEL_FD ? baked_model_source<float>(h, ncon_max, nefc_max) : baked_model_source<double>(h, ncon_max, nefc_max);
   s += "#include \"mjb_kernels.hpp\"\n";
   return s;
 }
@@ -463,15 +507,14 @@ static void choose_schedule(mjbData* d, StepArgs& a) {
     const char* e1 = std::getenv("MJB_CHUNK_STEPS"); const char* e2 = std::getenv("MJB_FAIR_BIT");
     d->sched_chunk = e1 ? std::atoi(e1) : -2; d->fair_bit = e2 ? std::atoi(e2) : -2;
   }
-  const int epb = 64 / d->G;
+  const int epb = 64 / d->cfg.G;
   const long nblk = (d->batch + epb - 1) / epb;
   if (d->step_slots < 0) {
-    int ncu = 0, nb = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess || ncu < 1) ncu = 256;
-    if (d->dtype == MJB_F32 && d->spec_fn) {
-      if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, d->spec_fn, 64, (size_t)epb * d->Lf.bytes) != hipSuccess) nb = 0;
-    } else nb = d->dtype == MJB_F32 ? step_blocks_per_cu<float, float>(d->G, d->Lf) : step_blocks_per_cu<double, double>(d->G, d->Ld);
-    d->step_slots = nb > 0 ? (long)nb * ncu : 0;              // 0 = unknown: keep the static map
+    int nb = 0;
+    if (hipFunction_t fn = d->spec[MJB_KERNEL_STEP].fn) {
+      if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64, (size_t)epb * d->cfg.Lf.bytes) != hipSuccess) nb = 0;
+    } else nb = d->dtype == MJB_F32 ? step_blocks_per_cu<float, float>(d->cfg.G, d->cfg.Lf) : step_blocks_per_cu<double, double>(d->cfg.G, d->cfg.Ld);
+    d->step_slots = nb > 0 ? (long)nb * d->ncu : 0;           // 0 = unknown: keep the static map
   }
   a.fair_bit = d->fair_bit >= 0 ? d->fair_bit : 15;            // 2^15 x 10 ns = 0.33 ms per turn
   a.nblk = (int)nblk; a.grid_blocks = d->step_slots > 0 && d->step_slots < nblk ? (int)d->step_slots : (int)nblk;
@@ -502,6 +545,15 @@ int engine_check(const mjbData* d) {
   return MJB_OK;
 }
 
+// A per-model specialised step kernel (MJB_KERNEL_STEP or MJB_KERNEL_STEP2): the arguments of the generic fp32 kernel, lg = its layout
+hipError_t launch_spec_step(mjbData* d, int kind, const Lay* lg, const DevDebug<float>& dbg, const StepArgs& a, const ObsSpecDev& obs,
+                            void* obs_out, unsigned grid, unsigned block, size_t lds) {
+  const DevModel<float>* mg = d->mf_dev;
+  DevData<float> dv = d->df; DevDebug<float> dbgarg = dbg; StepArgs av = a; ObsSpecDev ov = obs; float* oo = (float*)obs_out;
+  void* args[] = {(void*)&mg, (void*)&lg, (void*)&dv, (void*)&dbgarg, (void*)&av, (void*)&ov, (void*)&oo};
+  return hipModuleLaunchKernel(d->spec[kind].fn, grid, 1, 1, block, 1, 1, (unsigned)lds, d->stream, args, nullptr);
+}
+
 int launch(mjbData* d, const StepArgs& a_in, const ObsSpecDev& obs, void* obs_out, bool debug) {
   int rc = engine_check(d);                                    // no further launches on top of a failed one
   if (rc != MJB_OK) return rc;
@@ -519,7 +571,7 @@ int launch(mjbData* d, const StepArgs& a_in, const ObsSpecDev& obs, void* obs_ou
   }
   if (a.chunk_steps > 0) chunk_plan_counts(a.nstep, a.chunk_steps, a.nuniform, a.nchunk);
   if (a.mode == 0) {
-    const int epb = 64 / d->G;
+    const int epb = 64 / d->cfg.G;
     d->last_sched[0] = a.nstep; d->last_sched[1] = (d->batch + epb - 1) / epb; d->last_sched[2] = (int)(d->step_slots > 0 ? d->step_slots : 0);
     d->last_sched[3] = a.chunk_steps; d->last_sched[4] = a.fair_bit;
   }
@@ -550,43 +602,31 @@ int launch(mjbData* d, const StepArgs& a_in, const ObsSpecDev& obs, void* obs_ou
   // Two waves per environment (env_run2) when the batch leaves at least half of the step kernel's resident slots empty: stepping
   // launches only (mode 0, no debug dumps), fp32, one wave per environment, nv <= 32, Euler.
   bool two = false;
-  if (a.mode == 0 && !debug && d->dtype == MJB_F32 && d->Lf2.bytes > 0 && a.chunk_steps == 0) {
+  if (a.mode == 0 && !debug && d->dtype == MJB_F32 && d->cfg.Lf2.bytes > 0 && a.chunk_steps == 0) {
     if (d->two_wave == -1) { const char* e2 = std::getenv("MJB_TWO_WAVE"); d->two_wave = e2 ? (std::atoi(e2) ? 1 : 0) : 2; }
-    if (d->ncu <= 0 && (hipDeviceGetAttribute(&d->ncu, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess || d->ncu < 1)) d->ncu = 256;
-    const int ncu = d->ncu;
     // every environment must be resident at once: the kernel is built for two waves per SIMD (__launch_bounds__(128, 2)), i.e. four
     // workgroups per CU.  Measured on the humanoid (profiles/r02_two_wave.log): x1.15 .. 1.18 up to 512 environments (two SIMDs per
     // environment), x1.12 at 768, x1.09 at 1024, x0.7 beyond (two rounds)
-    long wg_per_cu = d->Lf2.bytes > 0 ? (160L * 1024) / d->Lf2.bytes : 0;
+    long wg_per_cu = d->cfg.Lf2.bytes > 0 ? (160L * 1024) / d->cfg.Lf2.bytes : 0;
     if (wg_per_cu > 4) wg_per_cu = 4;
-    two = d->two_wave == 1 || (d->two_wave == 2 && (long)d->batch <= wg_per_cu * ncu);
+    two = d->two_wave == 1 || (d->two_wave == 2 && (long)d->batch <= wg_per_cu * d->ncu);
   }
   d->last_sched[5] = two ? 1 : 0;
+  DevDebug<float> nodbg; std::memset(&nodbg, 0, sizeof(nodbg));
   if (two) {
     a.fair_bit = 0;
-    if (d->spec2_fn) {
-      DevDebug<float> dbgarg; std::memset(&dbgarg, 0, sizeof(dbgarg));
-      const DevModel<float>* mg = d->mf_dev; const Lay* lg = d->Lf2_dev;
-      DevData<float> dv = d->df; StepArgs av = a; ObsSpecDev ov = obs; float* oo = (float*)obs_out;
-      void* args[] = {(void*)&mg, (void*)&lg, (void*)&dv, (void*)&dbgarg, (void*)&av, (void*)&ov, (void*)&oo};
-      e = hipModuleLaunchKernel(d->spec2_fn, (unsigned)d->batch, 1, 1, 128, 1, 1, (unsigned)d->Lf2.bytes, d->stream, args, nullptr);
-    } else e = launch_step2<float, float>(d->mf_dev, d->Lf2_dev, d->Lf2, d->df, a, obs, (float*)obs_out, d->stream);
-  } else
-  if (d->dtype == MJB_F32 && d->spec_fn) {               // per-model specialised kernel: same arguments, same grid
-    DevDebug<float> dbgarg; std::memset(&dbgarg, 0, sizeof(dbgarg));
-    if (debug) dbgarg = d->dbgf;
-    const DevModel<float>* mg = d->mf_dev; const Lay* lg = d->Lf_dev;
-    DevData<float> dv = d->df; StepArgs av = a; ObsSpecDev ov = obs; float* oo = (float*)obs_out;
-    void* args[] = {(void*)&mg, (void*)&lg, (void*)&dv, (void*)&dbgarg, (void*)&av, (void*)&ov, (void*)&oo};
-    const int epb = 64 / d->G;
+    if (d->spec[MJB_KERNEL_STEP2].fn)
+      e = launch_spec_step(d, MJB_KERNEL_STEP2, d->Lf2_dev, nodbg, a, obs, obs_out, (unsigned)d->batch, 128, (size_t)d->cfg.Lf2.bytes);
+    else e = launch_step2<float, float>(d->mf_dev, d->Lf2_dev, d->cfg.Lf2, d->df, a, obs, (float*)obs_out, d->stream);
+  } else if (d->spec[MJB_KERNEL_STEP].fn) {                  // per-model specialised kernel: same arguments, same grid
+    const int epb = 64 / d->cfg.G;
     const unsigned grid = a.chunk_steps > 0 ? (unsigned)a.grid_blocks : (unsigned)((d->batch + epb - 1) / epb);
-    e = hipModuleLaunchKernel(d->spec_fn, grid, 1, 1, 64, 1, 1, (unsigned)((size_t)epb * d->Lf.bytes), d->stream, args, nullptr);
+    e = launch_spec_step(d, MJB_KERNEL_STEP, d->Lf_dev, debug ? d->dbgf : nodbg, a, obs, obs_out, grid, 64, (size_t)epb * d->cfg.Lf.bytes);
   } else if (d->dtype == MJB_F32) {
-    DevDebug<float> none; std::memset(&none, 0, sizeof(none));
-    e = launch_step<float, float>(d->G, d->mf_dev, d->Lf_dev, d->Lf, d->df, debug ? d->dbgf : none, a, obs, (float*)obs_out, d->stream);
+    e = launch_step<float, float>(d->cfg.G, d->mf_dev, d->Lf_dev, d->cfg.Lf, d->df, debug ? d->dbgf : nodbg, a, obs, (float*)obs_out, d->stream);
   } else {
     DevDebug<double> none; std::memset(&none, 0, sizeof(none));
-    e = launch_step<double, double>(d->G, d->md_dev, d->Ld_dev, d->Ld, d->dd, debug ? d->dbgd : none, a, obs, (double*)obs_out, d->stream);
+    e = launch_step<double, double>(d->cfg.G, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, debug ? d->dbgd : none, a, obs, (double*)obs_out, d->stream);
   }
   if (e != hipSuccess) {
     // the device counter may or may not have been rewound above and no workgroup drew a ticket: start the next ticket launch from a
@@ -673,39 +713,19 @@ int mjb_data_create(mjbModel* m, int batch, int dtype, int lanes, int nconmax, i
   if (device < 0 || device >= ndev) return fail(MJB_ERR_ARG, "device index out of range");
   HIPCHK(hipSetDevice(device));
   const HostModel& h = m->h;
-  lanes = auto_lanes(h, lanes);
-  if (lanes != 8 && lanes != 16 && lanes != 64) return fail(MJB_ERR_ARG, "lanes must be 8, 16 or 64");
+  Config cfg;
+  std::string err;
+  if (!derive_config(h, dtype, lanes, nconmax, nefcmax, cfg, err)) return fail(MJB_ERR_ARG, err);
   mjbData* d = new mjbData();
-  d->model = m; d->batch = batch; d->dtype = dtype; d->G = lanes; d->device = device; d->env0 = env0; d->stream = nullptr;
-  // Caps on contacts / constraint rows held in LDS per environment.  Explicit values are taken as given.  Default: the
-  // model's own worst case when that is small (<= 96 rows, <= 32 contacts); otherwise the largest (rows <= 96, contacts =
-  // 3/8 rows) that still lets 8 fp32 (4 fp64) wavefronts share one CU's 160 KiB — the occupancy step that matters most
-  // for throughput (profiles/).  Overflow drops rows and is COUNTED.
-  choose_caps(h, dtype, lanes, nconmax, nefcmax, d->ncon_max, d->nefc_max);
-  fill_dev_model<float>(h, d->alloc, d->ncon_max, d->nefc_max, d->mf);
-  fill_dev_model<double>(h, d->alloc, d->ncon_max, d->nefc_max, d->md);
+  d->model = m; d->batch = batch; d->dtype = dtype; d->cfg = cfg; d->device = device; d->env0 = env0; d->stream = nullptr;
+  if (hipDeviceGetAttribute(&d->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || d->ncu < 1) d->ncu = 256;
+  fill_dev_model<float>(h, d->alloc, cfg.ncon_max, cfg.nefc_max, d->mf);
+  fill_dev_model<double>(h, d->alloc, cfg.ncon_max, cfg.nefc_max, d->md);
   if (!d->alloc.ok) { mjb_data_free(d); return fail(MJB_ERR_DEVICE, "device allocation of the model failed"); }
-  d->Lf = make_layout(h, d->ncon_max, d->nefc_max, sizeof(float));
-  d->Ld = make_layout(h, d->ncon_max, d->nefc_max, sizeof(double));
-  // the float64 FD / Jacobian kernels may need more lanes per environment than the step kernel to fit LDS
-  d->G_fd = d->G;
-  while (d->G_fd < 64 && (size_t)(64 / d->G_fd) * (size_t)d->Ld.bytes > 160 * 1024) d->G_fd = d->G_fd == 8 ? 16 : 64;
-  size_t lds = (size_t)(64 / d->G) * (size_t)(dtype == MJB_F32 ? d->Lf.bytes : d->Ld.bytes);
-  if (lds > 160 * 1024 || (size_t)(64 / d->G_fd) * (size_t)d->Ld.bytes > 160 * 1024) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "per-workgroup LDS %zu B exceeds 160 KiB (lower nconmax/nefcmax or use more lanes)", lds);
-    mjb_data_free(d);
-    return fail(MJB_ERR_ARG, buf);
-  }
-  std::memset(&d->Lf2, 0, sizeof(Lay));
-  if (dtype == MJB_F32 && d->G == 64 && h.nv <= 32 && h.integrator != INT_RK4) {
-    d->Lf2 = make_layout(h, d->ncon_max, d->nefc_max, sizeof(float), true);
-    if ((size_t)d->Lf2.bytes > 64 * 1024) std::memset(&d->Lf2, 0, sizeof(Lay));       // (never for the models this path is for)
-  }
   if (dev_alloc(d, &d->mf_dev, 1) || dev_alloc(d, &d->md_dev, 1) || dev_alloc(d, &d->Lf_dev, 1) || dev_alloc(d, &d->Ld_dev, 1) || dev_alloc(d, &d->Lf2_dev, 1) ||
-      hipMemcpy(d->Lf2_dev, &d->Lf2, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d->Lf_dev, &d->Lf, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d->Ld_dev, &d->Ld, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess) {
+      hipMemcpy(d->Lf2_dev, &d->cfg.Lf2, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d->Lf_dev, &d->cfg.Lf, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d->Ld_dev, &d->cfg.Ld, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess) {
     mjb_data_free(d);
     return fail(MJB_ERR_DEVICE, "device allocation of the model descriptors failed");
   }
@@ -719,11 +739,9 @@ int mjb_data_create(mjbModel* m, int batch, int dtype, int lanes, int nconmax, i
 }
 
 void mjb_data_free(mjbData* d) {
-  if (d && d->spec_mod) { hipModuleUnload(d->spec_mod); d->spec_mod = nullptr; d->spec_fn = nullptr; }
-  if (d && d->fd_spec_mod) { hipModuleUnload(d->fd_spec_mod); d->fd_spec_mod = nullptr; d->fd_spec_fn = nullptr; }
-  if (d && d->spec2_mod) { hipModuleUnload(d->spec2_mod); d->spec2_mod = nullptr; d->spec2_fn = nullptr; }
   if (!d) return;
   (void)hipSetDevice(d->device);
+  for (auto& k : d->spec) if (k.mod) (void)hipModuleUnload(k.mod);
   for (void* p : d->owned) (void)hipFree(p);
   if (d->mirror_host) (void)hipHostFree(d->mirror_host);
   std::free(d->mirror_shadow);
@@ -761,10 +779,10 @@ int mjb_data_info(mjbData* d, int* batch, int* dtype, int* lanes, int* nconmax, 
   if (!d) return fail(MJB_ERR_ARG, "data is NULL");
   if (batch) *batch = d->batch;
   if (dtype) *dtype = d->dtype;
-  if (lanes) *lanes = d->G;
-  if (nconmax) *nconmax = d->ncon_max;
-  if (nefcmax) *nefcmax = d->nefc_max;
-  if (lds_bytes_per_env) *lds_bytes_per_env = d->dtype == MJB_F32 ? d->Lf.bytes : d->Ld.bytes;
+  if (lanes) *lanes = d->cfg.G;
+  if (nconmax) *nconmax = d->cfg.ncon_max;
+  if (nefcmax) *nefcmax = d->cfg.nefc_max;
+  if (lds_bytes_per_env) *lds_bytes_per_env = d->dtype == MJB_F32 ? d->cfg.Lf.bytes : d->cfg.Ld.bytes;
   return MJB_OK;
 }
 
@@ -871,129 +889,57 @@ static StepArgs make_args(mjbData* d, int nstep, int ctrl_mode, unsigned seed, u
   return a;
 }
 
-long mjb_model_spec_source(mjbModel* m, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap) {
-  if (!m) { fail(MJB_ERR_ARG, "model is NULL"); return -1; }
-  if (dtype != MJB_F32) { fail(MJB_ERR_ARG, "only the float32 step kernel is specialised"); return -1; }
-  const HostModel& h = m->h;
-  lanes = auto_lanes(h, lanes);
-  if (lanes != 8 && lanes != 16 && lanes != 64) { fail(MJB_ERR_ARG, "lanes must be 8, 16 or 64"); return -1; }
-  int nc, ne;
-  choose_caps(h, dtype, lanes, nconmax, nefcmax, nc, ne);
-  const std::string src = spec_source(h, make_layout(h, nc, ne, sizeof(float)), lanes, nc, ne);
+// the specialised kernels: model-level and data-level sources come from the same configuration (derive_config) and the same target
+static long kernel_source(const HostModel& h, const Config& c, int dtype, int kind, char* buf, long cap) {
+  if (check_kind(c, dtype, kind) != MJB_OK) return -1;
+  const std::string src = spec_source(h, c, dtype, kind);
   if (buf && cap > (long)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
   return (long)src.size();
 }
 
-// the finite-difference kernel's translation unit for the creation arguments a data object of this model would get (no GPU needed:
-// the same caps, float64 layout and lane-group width mjb_data_create derives)
-long mjb_model_fd_spec_source(mjbModel* m, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap) {
+long mjb_model_kernel_source(mjbModel* m, int kind, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap) {
   if (!m) { fail(MJB_ERR_ARG, "model is NULL"); return -1; }
   if (dtype != MJB_F32 && dtype != MJB_F64) { fail(MJB_ERR_ARG, "dtype must be MJB_F32 or MJB_F64"); return -1; }
-  const HostModel& h = m->h;
-  lanes = auto_lanes(h, lanes);
-  if (lanes != 8 && lanes != 16 && lanes != 64) { fail(MJB_ERR_ARG, "lanes must be 8, 16 or 64"); return -1; }
-  int nc, ne;
-  choose_caps(h, dtype, lanes, nconmax, nefcmax, nc, ne);
-  const Lay Ld = make_layout(h, nc, ne, sizeof(double));
-  int gfd = lanes;
-  while (gfd < 64 && (size_t)(64 / gfd) * (size_t)Ld.bytes > 160 * 1024) gfd = gfd == 8 ? 16 : 64;
-  const std::string src = spec_source(h, Ld, gfd, nc, ne, 2, dtype == MJB_F32 ? "float" : "double");
-  if (buf && cap > (long)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
-  return (long)src.size();
+  Config c;
+  std::string err;
+  if (!derive_config(m->h, dtype, lanes, nconmax, nefcmax, c, err)) { fail(MJB_ERR_ARG, err); return -1; }
+  return kernel_source(m->h, c, dtype, kind, buf, cap);
 }
 
-long mjb_spec_source(mjbData* d, char* buf, long cap) {
+long mjb_kernel_source(mjbData* d, int kind, char* buf, long cap) {
   if (!d) { fail(MJB_ERR_ARG, "data is NULL"); return -1; }
-  if (d->dtype != MJB_F32) { fail(MJB_ERR_ARG, "only the float32 step kernel is specialised"); return -1; }
-  const std::string src = spec_source(d->model->h, d->Lf, d->G, d->ncon_max, d->nefc_max);
-  if (buf && cap > (long)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
-  return (long)src.size();
+  return kernel_source(d->model->h, d->cfg, d->dtype, kind, buf, cap);
 }
 
-int mjb_spec_load(mjbData* d, const void* image, long nbytes) {
+// Unload a kind's module (after the stream has drained).  The step kernel's occupancy decides the ticket map's grid: re-query it.
+static void drop_kernel(mjbData* d, int kind) {
+  if (!d->spec[kind].mod) return;
+  (void)hipModuleUnload(d->spec[kind].mod);
+  d->spec[kind].mod = nullptr; d->spec[kind].fn = nullptr;
+  if (kind == MJB_KERNEL_STEP) d->step_slots = -1;
+}
+
+int mjb_kernel_load(mjbData* d, int kind, const void* image, long nbytes) {
   if (!d || !image || nbytes <= 0) return fail(MJB_ERR_ARG, "NULL argument");
-  if (d->dtype != MJB_F32) return fail(MJB_ERR_ARG, "only the float32 step kernel is specialised");
+  int rc = check_kind(d->cfg, d->dtype, kind);
+  if (rc != MJB_OK) return rc;
   HIPCHK(hipSetDevice(d->device));
   HIPCHK(hipStreamSynchronize(d->stream));
-  if (d->spec_mod) { hipModuleUnload(d->spec_mod); d->spec_mod = nullptr; d->spec_fn = nullptr; }
+  drop_kernel(d, kind);
   hipModule_t mod; hipFunction_t fn;
   hipError_t e = hipModuleLoadData(&mod, image);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("hipModuleLoadData: ") + hipGetErrorString(e));
-  e = hipModuleGetFunction(&fn, mod, "mjb_k_step_spec");
-  if (e != hipSuccess) { hipModuleUnload(mod); return fail(MJB_ERR_DEVICE, "code object has no mjb_k_step_spec kernel"); }
-  d->spec_mod = mod; d->spec_fn = fn; d->step_slots = -1;        // occupancy of the kernel in use changed
+  e = hipModuleGetFunction(&fn, mod, kKinds[kind].symbol);
+  if (e != hipSuccess) { (void)hipModuleUnload(mod); return fail(MJB_ERR_DEVICE, std::string("code object has no ") + kKinds[kind].symbol + " kernel"); }
+  d->spec[kind].mod = mod; d->spec[kind].fn = fn;
+  if (kind == MJB_KERNEL_STEP) d->step_slots = -1;
   return MJB_OK;
 }
 
-int mjb_spec_unload(mjbData* d) {
+int mjb_kernel_unload(mjbData* d, int kind) {
   if (!d) return fail(MJB_ERR_ARG, "data is NULL");
-  if (d->spec_mod) { HIPCHK(hipStreamSynchronize(d->stream)); hipModuleUnload(d->spec_mod); d->spec_mod = nullptr; d->spec_fn = nullptr; d->step_slots = -1; }
-  return MJB_OK;
-}
-
-// the two-wave step kernel (small batches) of this data object / of a model's default creation arguments
-long mjb_step2_spec_source(mjbData* d, char* buf, long cap) {
-  if (!d) { fail(MJB_ERR_ARG, "data is NULL"); return -1; }
-  if (d->Lf2.bytes <= 0) { fail(MJB_ERR_ARG, "the two-wave step kernel does not apply to this data object (fp32, one wave per environment, nv <= 32, Euler)"); return -1; }
-  const std::string src = spec_source(d->model->h, d->Lf2, 64, d->ncon_max, d->nefc_max, 3, "float");
-  if (buf && cap > (long)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
-  return (long)src.size();
-}
-long mjb_model_step2_spec_source(mjbModel* m, int lanes, int nconmax, int nefcmax, char* buf, long cap) {
-  if (!m) { fail(MJB_ERR_ARG, "model is NULL"); return -1; }
-  const HostModel& h = m->h;
-  lanes = auto_lanes(h, lanes);
-  if (lanes != 64 || h.nv > 32 || h.integrator == INT_RK4) { fail(MJB_ERR_ARG, "the two-wave step kernel does not apply to this model"); return -1; }
-  int nc, ne;
-  choose_caps(h, MJB_F32, lanes, nconmax, nefcmax, nc, ne);
-  const std::string src = spec_source(h, make_layout(h, nc, ne, sizeof(float), true), 64, nc, ne, 3, "float");
-  if (buf && cap > (long)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
-  return (long)src.size();
-}
-int mjb_step2_spec_load(mjbData* d, const void* image, long nbytes) {
-  if (!d || !image || nbytes <= 0) return fail(MJB_ERR_ARG, "NULL argument");
-  if (d->Lf2.bytes <= 0) return fail(MJB_ERR_ARG, "the two-wave step kernel does not apply to this data object");
-  HIPCHK(hipSetDevice(d->device));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  if (d->spec2_mod) { hipModuleUnload(d->spec2_mod); d->spec2_mod = nullptr; d->spec2_fn = nullptr; }
-  hipModule_t mod; hipFunction_t fn;
-  hipError_t e = hipModuleLoadData(&mod, image);
-  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("hipModuleLoadData: ") + hipGetErrorString(e));
-  e = hipModuleGetFunction(&fn, mod, "mjb_k_step2_spec");
-  if (e != hipSuccess) { hipModuleUnload(mod); return fail(MJB_ERR_DEVICE, "code object has no mjb_k_step2_spec kernel"); }
-  d->spec2_mod = mod; d->spec2_fn = fn;
-  return MJB_OK;
-}
-int mjb_step2_spec_unload(mjbData* d) {
-  if (!d) return fail(MJB_ERR_ARG, "data is NULL");
-  if (d->spec2_mod) { HIPCHK(hipStreamSynchronize(d->stream)); hipModuleUnload(d->spec2_mod); d->spec2_mod = nullptr; d->spec2_fn = nullptr; }
-  return MJB_OK;
-}
-
-long mjb_fd_spec_source(mjbData* d, char* buf, long cap) {
-  if (!d) { fail(MJB_ERR_ARG, "data is NULL"); return -1; }
-  const std::string src = spec_source(d->model->h, d->Ld, d->G_fd, d->ncon_max, d->nefc_max, 2, d->dtype == MJB_F32 ? "float" : "double");
-  if (buf && cap > (long)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
-  return (long)src.size();
-}
-
-int mjb_fd_spec_load(mjbData* d, const void* image, long nbytes) {
-  if (!d || !image || nbytes <= 0) return fail(MJB_ERR_ARG, "NULL argument");
-  HIPCHK(hipSetDevice(d->device));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  if (d->fd_spec_mod) { hipModuleUnload(d->fd_spec_mod); d->fd_spec_mod = nullptr; d->fd_spec_fn = nullptr; }
-  hipModule_t mod; hipFunction_t fn;
-  hipError_t e = hipModuleLoadData(&mod, image);
-  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("hipModuleLoadData: ") + hipGetErrorString(e));
-  e = hipModuleGetFunction(&fn, mod, "mjb_k_fd_spec");
-  if (e != hipSuccess) { hipModuleUnload(mod); return fail(MJB_ERR_DEVICE, "code object has no mjb_k_fd_spec kernel"); }
-  d->fd_spec_mod = mod; d->fd_spec_fn = fn;
-  return MJB_OK;
-}
-
-int mjb_fd_spec_unload(mjbData* d) {
-  if (!d) return fail(MJB_ERR_ARG, "data is NULL");
-  if (d->fd_spec_mod) { HIPCHK(hipStreamSynchronize(d->stream)); hipModuleUnload(d->fd_spec_mod); d->fd_spec_mod = nullptr; d->fd_spec_fn = nullptr; }
+  if (!valid_kind(kind)) return fail(MJB_ERR_ARG, "unknown kernel kind (MJB_KERNEL_STEP, MJB_KERNEL_FD or MJB_KERNEL_STEP2)");
+  if (d->spec[kind].mod) { HIPCHK(hipStreamSynchronize(d->stream)); drop_kernel(d, kind); }
   return MJB_OK;
 }
 
@@ -1189,31 +1135,29 @@ static int transition_fd_impl(mjbData* d, double eps, int centered) {
   // at most 8; a single environment keeps one column per job (latency over throughput)
   int chunk = 8;
   {
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess || ncu < 1) ncu = 256;
-    const size_t per_wg = (size_t)(64 / d->G_fd) * (size_t)d->Ld.bytes;
+    const size_t per_wg = (size_t)(64 / d->cfg.G_fd) * (size_t)d->cfg.Ld.bytes;
     size_t wg_per_cu = per_wg ? (size_t)160 * 1024 / per_wg : 8;
     if (wg_per_cu > 32) wg_per_cu = 32;
     if (wg_per_cu < 1) wg_per_cu = 1;
-    const long slots = (long)wg_per_cu * ncu * (64 / d->G_fd);
+    const long slots = (long)wg_per_cu * d->ncu * (64 / d->cfg.G_fd);
     const long want = (long)B * ncol / (4 * slots);
     if (const char* e = std::getenv("MJB_FD_CHUNK")) chunk = std::atoi(e);        // experiments (scripts/gpu_fd_timing.py)
     else chunk = want < 1 ? 1 : (want > 8 ? 8 : (int)want);
   }
   hipError_t e;
-  if (d->fd_spec_fn) {                                          // per-model specialised kernel: same arguments, same grid as launch_fd_g
+  if (d->spec[MJB_KERNEL_FD].fn) {                              // per-model specialised kernel: same arguments, same grid as launch_fd_g
     if (chunk < 1) chunk = 1;
-    const int epb = 64 / d->G_fd;
+    const int epb = 64 / d->cfg.G_fd;
     const int njob = (1 + 2 * h.nu + chunk - 1) / chunk + (2 * h.nv + chunk - 1) / chunk + 2 * h.nv;
     const long ngroups = (long)d->batch * njob;
     const DevModel<double>* mg = d->md_dev; const Lay* lg = d->Ld_dev;
     DevData<float> dvf = d->df; DevData<double> dvd = d->dd;
     int ncol_ = ncol, cv = chunk, cc = chunk; double eps_ = eps; double* yy = d->fd_y; int* vv = d->fd_valid;
     void* args[] = {(void*)&mg, (void*)&lg, d->dtype == MJB_F32 ? (void*)&dvf : (void*)&dvd, (void*)&ncol_, (void*)&eps_, (void*)&yy, (void*)&vv, (void*)&cv, (void*)&cc};
-    e = hipModuleLaunchKernel(d->fd_spec_fn, (unsigned)((ngroups + epb - 1) / epb), 1, 1, 64, 1, 1, (unsigned)((size_t)epb * d->Ld.bytes), d->stream, args, nullptr);
+    e = hipModuleLaunchKernel(d->spec[MJB_KERNEL_FD].fn, (unsigned)((ngroups + epb - 1) / epb), 1, 1, 64, 1, 1, (unsigned)((size_t)epb * d->cfg.Ld.bytes), d->stream, args, nullptr);
   } else
-  e = d->dtype == MJB_F32 ? launch_fd<double, float>(d->G_fd, d->md_dev, d->Ld_dev, d->Ld, d->df, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream)
-                          : launch_fd<double, double>(d->G_fd, d->md_dev, d->Ld_dev, d->Ld, d->dd, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream);
+  e = d->dtype == MJB_F32 ? launch_fd<double, float>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->df, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream)
+                          : launch_fd<double, double>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("fd launch: ") + hipGetErrorString(e));
   long nthreads = (long)B * nin;
   // a few environments (the reference's batch-1 loops with needs_linearization controllers): the combine kernel writes (A, B) straight
@@ -1289,8 +1233,8 @@ int mjb_jac(mjbData* d, int nreq, const int* kinds, const int* ids, double* jacp
   std::memcpy(d->jac_req_pin + nreq, ids, sizeof(int) * nreq);
   double *op = zero_copy ? d->jac_pin[0] : d->jac_dev[0], *orr = zero_copy ? d->jac_pin[1] : d->jac_dev[1];
   const int *dk = d->jac_req_pin, *di = d->jac_req_pin + nreq;
-  hipError_t e = d->dtype == MJB_F32 ? launch_jac<double, float>(d->G_fd, d->md_dev, d->Ld_dev, d->Ld, d->df, nreq, dk, di, op, orr, d->stream)
-                                     : launch_jac<double, double>(d->G_fd, d->md_dev, d->Ld_dev, d->Ld, d->dd, nreq, dk, di, op, orr, d->stream);
+  hipError_t e = d->dtype == MJB_F32 ? launch_jac<double, float>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->df, nreq, dk, di, op, orr, d->stream)
+                                     : launch_jac<double, double>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, nreq, dk, di, op, orr, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("jac launch: ") + hipGetErrorString(e));
   if (!zero_copy) {
     HIPCHK(hipMemcpyAsync(d->jac_pin[0], d->jac_dev[0], n * sizeof(double), hipMemcpyDeviceToHost, d->stream));

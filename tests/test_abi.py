@@ -71,7 +71,7 @@ def test_product_package_does_not_import_oracle():
 
 
 def test_specialised_kernel_source_and_cross_compile():
-    """Per-model specialisation (include/mjbatch.h mjb_model_spec_source): the generated translation unit pins the model's
+    """Per-model specialisation (include/mjbatch.h mjb_model_kernel_source): the generated translation unit pins the model's
     structural sizes and LDS offsets - never the run-time options - and cross-compiles for gfx950 without a GPU."""
     import torch  # noqa: F401  (one HIP runtime per process: torch first)
 
@@ -89,6 +89,28 @@ def test_specialised_kernel_source_and_cross_compile():
     blob = open(path, "rb").read()
     assert (blob[:4] == b"\x7fELF" or blob.startswith(b"__CLANG_OFFLOAD_BUNDLE__")) and b"mjb_k_step_spec" in blob and b"gfx950" in blob
     assert compile_spec(src) == path                      # cached
+
+
+def test_model_level_kernel_source_rejects_what_data_create_rejects():
+    """The model-level kernel sources derive the launch configuration in the same function as mjb_data_create: caps whose
+    per-workgroup LDS slice cannot fit are refused with mjb_data_create's error, and the two-wave kernel does not apply where its
+    flat layout exceeds 64 KiB, instead of yielding sources no data object will ever ask for."""
+    import torch  # noqa: F401
+
+    from mujoco_template_amd import mjcf
+    from mujoco_template_amd._capi import DeviceModel
+    from mujoco_template_amd.exceptions import ConfigError
+    from tests.conftest import MODELS
+
+    dm = DeviceModel(mjcf.compile_xml_path(MODELS["humanoid"]))
+    for source in (dm.spec_source, dm.fd_spec_source, dm.step2_spec_source):
+        assert source(lanes=64, nconmax=64, nefcmax=256) is not None
+    for source in (dm.spec_source, dm.fd_spec_source):
+        with pytest.raises(ConfigError, match="exceeds 160 KiB"):
+            source(lanes=8, nconmax=64, nefcmax=256)          # eight environments of 49 KB each in one workgroup
+    assert dm.step2_spec_source(lanes=8, nconmax=64, nefcmax=256) is None
+    assert "(m).nefc_max == 384" in dm.spec_source(lanes=64, nconmax=96, nefcmax=384)
+    assert dm.step2_spec_source(lanes=64, nconmax=96, nefcmax=384) is None             # flat layout above 64 KiB
 
 
 def test_specialised_kernel_drops_powf_only_when_the_model_allows_it():

@@ -824,6 +824,7 @@ def test_specialised_kernel_is_bitwise_identical_to_the_generic_one(world, name,
     for spec in (False, None):
         sim = BatchSim(dm, B, dtype="float32", specialize=spec)
         assert sim.specialized == (spec is None)
+        assert sim.spec_source() == dm.spec_source()            # the source build() pre-compiles from the model alone is the data object's
         sim.rollout(120, CTRL_RANDOM, seed=9, ctrl_scale=SCALE[name])
         res[spec] = (sim.get("qpos"), sim.get("qvel"), sim.get("qacc"), sim.get("xpos"), sim.counters())
     for a, b in zip(res[False][:4], res[None][:4]):
@@ -994,7 +995,7 @@ def test_two_wave_kernel_is_bitwise_identical_to_the_one_wave_kernel(world, spec
         assert sim.schedule_info()["waves_per_env"] == (1 if mode == "0" else 2)
         if mode == "policy":                                       # the source build() pre-compiles from the model alone is the data object's: a GPU box compiles nothing
             import mujoco_template_amd._capi as capi
-            assert capi._source_from(capi.load_library().mjb_step2_spec_source, sim.ptr) == dm.step2_spec_source()
+            assert capi._source_from(capi.load_library().mjb_kernel_source, sim.ptr, capi.MJB_KERNEL_STEP2) == dm.step2_spec_source()
         cn = sim.counters()
         res[mode] = [sim.get(k) for k in ("qpos", "qvel", "qacc", "qacc_warmstart", "ctrl", "time", "xpos", "subtree_com")] + out + [cn[k] for k in ("ncon", "nefc", "solver_niter")]
     for a, b in zip(res["0"], res["policy"]):
