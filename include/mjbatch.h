@@ -185,6 +185,18 @@ int mjb_step(mjbData* d, int nstep);
 int mjb_rollout(mjbData* d, int nstep, int ctrl_mode, unsigned seed, unsigned step0, double ctrl_scale,
                 const mjbObsSpec* spec, void* obs_out_dev, int obs_every);
 
+/* open-loop rollout: nstep x [ctrl <- ctrl_dev[s*step_stride + e*env_stride + a], mj_step]; ctrl_dev device memory in the data's
+ * dtype; strides in elements, >= 0 (0 = broadcast); spec / obs_out_dev / obs_every as in mjb_rollout.
+ * Replaces the controller-in-the-loop body of the reference (runtime.py:631-663 calling control.py:26-32) when the controls are known
+ * in advance (sampling planners, shooting): one launch for the whole rollout, s = 0 .. nstep-1 the step of this call, e the data's own
+ * (shard-local) environment index.  With an obs spec of qpos | qvel | sensordata | time and obs_every = 1, ring row t is the state
+ * after step t with the sensors of that step's forward pass (the order of mujoco.rollout).  data.ctrl ends as the last applied row.
+ * Checked before anything is launched (MJB_ERR_ARG, state and engine flags untouched): nstep >= 1, strides >= 0, ctrl_dev non-NULL
+ * when nu > 0, device-accessible memory of the data's device (hipPointerGetAttributes), and the highest element read,
+ * (nstep-1)*step_stride + (batch-1)*env_stride + nu-1, inside the allocation behind ctrl_dev (hipMemGetAddressRange). */
+int mjb_rollout_ctrl(mjbData* d, int nstep, const void* ctrl_dev, long step_stride, long env_stride,
+                     const mjbObsSpec* spec, void* obs_out_dev, int obs_every);
+
 /* gains of MJB_CTRL_FEEDBACK, host float64: K [nu, 2nv] row-major, u0 [nu], q0 [nq], v0 [nv] (NULL = zeros); shared by all environments */
 int mjb_set_feedback(mjbData* d, const double* K, const double* u0, const double* q0, const double* v0);
 

@@ -82,6 +82,7 @@ def load_library() -> ctypes.CDLL:
     L.mjb_inverse.argtypes = [vp]
     L.mjb_step.argtypes = [vp, ci]
     L.mjb_rollout.argtypes = [vp, ci, ci, cu, cu, cd, vp, vp, ci]
+    L.mjb_rollout_ctrl.argtypes = [vp, ci, vp, cl, cl, vp, vp, ci]
     L.mjb_set_feedback.argtypes = [vp, vp, vp, vp, vp]
     L.mjb_set_feedback.restype = ci
     L.mjb_set_feedback_noise.argtypes = [vp, vp, vp, ci, ci]
@@ -126,7 +127,7 @@ def load_library() -> ctypes.CDLL:
     L.mjb_step_host_auto.argtypes = [vp, ci, ci, ctypes.POINTER(ci)]
     for name in ("mjb_model_create", "mjb_model_set_disableactuator", "mjb_model_set_solver", "mjb_data_create", "mjb_set_stream",
                  "mjb_sync", "mjb_data_info", "mjb_array_ptr", "mjb_get_array", "mjb_set_array", "mjb_get_counters", "mjb_reset",
-                 "mjb_forward", "mjb_inverse", "mjb_kernel_load", "mjb_kernel_unload", "mjb_step", "mjb_rollout", "mjb_obs_spec_create", "mjb_obs_dim", "mjb_obs_gather",
+                 "mjb_forward", "mjb_inverse", "mjb_kernel_load", "mjb_kernel_unload", "mjb_step", "mjb_rollout", "mjb_rollout_ctrl", "mjb_obs_spec_create", "mjb_obs_dim", "mjb_obs_gather",
                  "mjb_transition_fd", "mjb_jac", "mjb_debug_forward", "mjb_debug_get", "mjb_model_field", "mjb_model_field_at", "mjb_model_save",
                  "mjb_model_load", "mjb_model_load_xml", "mjb_model_load_xml_string", "mjb_integrate_pos", "mjb_differentiate_pos", "mjb_host_view", "mjb_sync_to_host", "mjb_sync_to_device",
                  "mjb_step_host", "mjb_mirror_edited_mask", "mjb_mirror_commit", "mjb_step_host_auto", "mjb_engine_flags",
@@ -685,6 +686,41 @@ class BatchSim:
         _check(load_library().mjb_rollout(self.ptr, int(nstep), int(ctrl_mode), int(seed) & 0xFFFFFFFF, int(step0) & 0xFFFFFFFF,
                                           float(ctrl_scale), obs_spec.ptr if obs_spec else None,
                                           ctypes.c_void_p(obs_out_ptr) if obs_out_ptr else None, int(obs_every)))
+
+    def rollout_ctrl(self, nstep: int, ctrl, obs_spec: ObsSpecHandle | None = None, obs_out_ptr: int = 0, obs_every: int = 0) -> None:
+        """Open-loop rollout (``mjb_rollout_ctrl``): ``nstep`` steps, step ``s`` of environment ``e`` applying ``ctrl[e, s]`` (``[B, T, nu]``)
+        or ``ctrl[s]`` (``[T, nu]``, every environment), ``T >= nstep``.  ``ctrl`` is a torch tensor on this object's GPU in the data's
+        dtype; its own strides address it, so an ``expand``-ed tensor (stride 0) broadcasts without a copy.  The launch goes to torch's
+        current stream (``use_torch_stream``) and the tensor is kept referenced until the next call, so the caching allocator cannot
+        hand its memory out before the kernel has read it.  Observation ring as in ``rollout``."""
+        import torch
+
+        nstep = int(nstep)
+        if nstep < 1:
+            raise ConfigError("rollout_ctrl: nstep must be >= 1")
+        if not isinstance(ctrl, torch.Tensor):
+            raise ConfigError(f"rollout_ctrl: ctrl must be a torch tensor on cuda:{self.device}, got {type(ctrl).__name__}")
+        want = torch.float32 if self.dtype == "float32" else torch.float64
+        if ctrl.dtype != want:
+            raise ConfigError(f"rollout_ctrl: ctrl must have the data's dtype {want}, got {ctrl.dtype}")
+        if ctrl.device != torch.device(f"cuda:{self.device}"):
+            raise ConfigError(f"rollout_ctrl: ctrl must live on cuda:{self.device}, got {ctrl.device}")
+        nu = self.model.compiled.nu
+        if ctrl.ndim == 2 and ctrl.shape[1] == nu and ctrl.shape[0] >= nstep:
+            pass
+        elif ctrl.ndim == 3 and ctrl.shape[0] == self.batch and ctrl.shape[2] == nu and ctrl.shape[1] >= nstep:
+            pass
+        else:
+            raise ConfigError(f"rollout_ctrl: ctrl must have shape [T, {nu}] or [{self.batch}, T, {nu}] with T >= nstep = {nstep}, "
+                              f"got {list(ctrl.shape)}")
+        if nu > 1 and ctrl.stride(-1) != 1:
+            ctrl = ctrl.contiguous()
+        step_stride, env_stride = (ctrl.stride(0), 0) if ctrl.ndim == 2 else (ctrl.stride(1), ctrl.stride(0))
+        self.use_torch_stream()
+        self._ctrl_keep = ctrl                                      # alive at least until the next rollout_ctrl on this object
+        _check(load_library().mjb_rollout_ctrl(self.ptr, nstep, ctypes.c_void_p(ctrl.data_ptr()) if ctrl.numel() else None,
+                                               int(step_stride), int(env_stride), obs_spec.ptr if obs_spec else None,
+                                               ctypes.c_void_p(obs_out_ptr) if obs_out_ptr else None, int(obs_every)))
 
     def set_feedback(self, K: np.ndarray, u0: np.ndarray, q0: np.ndarray, v0: np.ndarray | None = None) -> None:
         m = self.model.compiled

@@ -996,6 +996,48 @@ int mjb_rollout(mjbData* d, int nstep, int ctrl_mode, unsigned seed, unsigned st
   return launch(d, a, obs, obs_out_dev, false);
 }
 
+// The control table of mjb_rollout_ctrl is read by the step kernel at caller-chosen offsets: everything it could touch is checked
+// here, before anything is launched, so that a bad pointer or extent comes back as MJB_ERR_ARG instead of a page fault on the device.
+static int check_ctrl_table(mjbData* d, int nstep, const void* ctrl_dev, long step_stride, long env_stride) {
+  const int nu = d->model->h.nu;
+  if (nu == 0) return MJB_OK;                                  // nothing is read: NULL allowed
+  if (!ctrl_dev) return fail(MJB_ERR_ARG, "mjb_rollout_ctrl: ctrl_dev is NULL");
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  hipError_t e = hipPointerGetAttributes(&at, ctrl_dev);
+  if (e != hipSuccess) (void)hipGetLastError();                // pageable host memory: an error on some runtimes, "unregistered" on others
+  const bool dev_mem = e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == d->device;
+  const bool pinned = e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer == ctrl_dev;
+  if (!dev_mem && !pinned)
+    return fail(MJB_ERR_ARG, "mjb_rollout_ctrl: ctrl_dev is not device-accessible memory of this data object's device");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ctrl_dev);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(MJB_ERR_ARG, "mjb_rollout_ctrl: no allocation found behind ctrl_dev"); }
+  // highest element read: (nstep-1) step_stride + (batch-1) env_stride + nu-1, in 128-bit arithmetic (no overflow whatever the strides)
+  const __int128 hi = (__int128)(nstep - 1) * step_stride + (__int128)(d->batch - 1) * env_stride + (nu - 1);
+  const __int128 esize = d->dtype == MJB_F32 ? 4 : 8;
+  const __int128 end = (__int128)(uintptr_t)ctrl_dev + (hi + 1) * esize, limit = (__int128)(uintptr_t)base + (__int128)size;
+  if ((uintptr_t)ctrl_dev < (uintptr_t)base || end > limit)
+    return fail(MJB_ERR_ARG, "mjb_rollout_ctrl: the control table's extent (nstep, batch, strides) lies beyond its allocation");
+  return MJB_OK;
+}
+
+int mjb_rollout_ctrl(mjbData* d, int nstep, const void* ctrl_dev, long step_stride, long env_stride,
+                     const mjbObsSpec* spec, void* obs_out_dev, int obs_every) {
+  if (!d) return fail(MJB_ERR_ARG, "data is NULL");
+  if (nstep < 1) return fail(MJB_ERR_ARG, "nstep must be >= 1");
+  if (step_stride < 0 || env_stride < 0) return fail(MJB_ERR_ARG, "mjb_rollout_ctrl: strides must be >= 0");
+  HIPCHK(hipSetDevice(d->device));
+  int rc = check_ctrl_table(d, nstep, ctrl_dev, step_stride, env_stride);
+  if (rc != MJB_OK) return rc;
+  StepArgs a = make_args(d, nstep, CTRL_SEQUENCE, 0, 0, 1.0, 0);
+  a.ctrl_seq = ctrl_dev; a.ctrl_step_stride = step_stride; a.ctrl_env_stride = env_stride;
+  ObsSpecDev obs; std::memset(&obs, 0, sizeof(obs));
+  if (spec && obs_out_dev && obs_every > 0) { obs = spec->dev; a.obs_every = obs_every; }
+  return launch(d, a, obs, obs_out_dev, false);
+}
+
 int mjb_set_feedback(mjbData* d, const double* K, const double* u0, const double* q0, const double* v0) {
   if (!d || !K || !u0 || !q0) return fail(MJB_ERR_ARG, "NULL argument");
   const HostModel& h = d->model->h;

@@ -23,10 +23,12 @@
 #include "mjb_hostemu.hpp"
 #define MJB_DEV static inline
 #define MJB_DEVM inline
+#define MJB_DEV_CALL static __attribute__((noinline))
 #else
 #include <hip/hip_runtime.h>
 #define MJB_DEV __device__ __forceinline__
 #define MJB_DEVM __device__ __forceinline__
+#define MJB_DEV_CALL __device__ __attribute__((noinline))     // a real call: code of a rare branch kept out of the step loop's register allocation
 #endif
 
 // Wave-level intrinsics behind macros: the device build expands them to the gfx950 builtins (unchanged code), the test-only host
@@ -2563,6 +2565,14 @@ template <typename T, int G> MJB_DEV void feedback_ctrl(Ctx<T>& c, ArgsRef a, un
   gsync<G>();
 }
 
+// Open-loop ctrl (CTRL_SEQUENCE, mjb_rollout_ctrl): row (step, env) of the caller's control tensor, read in the storage dtype.  Not
+// inlined: inlined, its address arithmetic shifts the register allocation of the whole step loop (humanoid fp32 specialised kernel:
+// +2 VGPR / +8 SGPR spills) and costs the other ctrl modes; as a call it leaves their code as it was.
+template <typename T, typename TS, int G> MJB_DEV_CALL void sequence_ctrl(T* ctrl, ArgsRef a, int nu, int env, int step, int lane) {
+  const TS* src = (const TS*)a.ctrl_seq + (long)step * a.ctrl_step_stride + (long)env * a.ctrl_env_stride;
+  for (int i = lane; i < nu; i += G) ctrl[i] = (T)src[i];
+}
+
 // mj_inverse after forward() with skip_dynamics (reference setpoints.py:29-31): the constraint force follows in closed
 // form from jar = J qacc - aref (one-sided quadratic rows: force = -D jar where jar < 0), then
 // qfrc_inverse = M qacc + qfrc_bias - qfrc_passive - J^T force.  Also writes the dense actuator moment [nu, nv]
@@ -2856,6 +2866,10 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
         for (int rp_ = MJB_REP_N(c, REP_CTRL); rp_ > 0; rp_--) random_ctrl<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane);
         gsync<G>();
       } else if (a.ctrl_mode == CTRL_FEEDBACK) feedback_ctrl<T, G>(c, a, a.env0 + (unsigned)env, a.step0 + (unsigned)s);
+      else if (a.ctrl_mode == CTRL_SEQUENCE) {             // s: the launch-local step index, also in ticket mode
+        sequence_ctrl<T, TS, G>(w + L.ctrl, a, nu, env, s, lane);
+        gsync<G>();
+      }
     }
     bool retried = false;
     for (int st = 0; st < nstage; st++) {
@@ -3018,6 +3032,10 @@ MJB_DEV void env_run2(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, 
         random_ctrl<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane);
         gsync<G>();
       } else if (a.ctrl_mode == CTRL_FEEDBACK) feedback_ctrl<T, G>(c, a, a.env0 + (unsigned)env, a.step0 + (unsigned)s);
+      else if (a.ctrl_mode == CTRL_SEQUENCE) {
+        sequence_ctrl<T, TS, G>(w + L.ctrl, a, nu, env, s, lane);
+        gsync<G>();
+      }
     }
     mjb_f16v inv;
     for (int pass = 0; pass < 2; pass++) {                      // pass 1 only after a bad-acceleration reset (like k_step's retry)

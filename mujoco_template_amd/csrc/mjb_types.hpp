@@ -24,7 +24,7 @@ enum { TRN_JOINT = 0, TRN_SITE = 4 };
 enum { INT_EULER = 0, INT_RK4 = 1 };
 enum { SENS_JOINTPOS = 0, SENS_GYRO, SENS_ACCEL, SENS_FRAMEQUAT };
 enum { EFC_LIMIT_JOINT = 0, EFC_LIMIT_TENDON = 1, EFC_CONTACT_FRICTIONLESS = 2, EFC_CONTACT_PYRAMIDAL = 3 };
-enum { CTRL_KEEP = 0, CTRL_ZERO = 1, CTRL_RANDOM = 2, CTRL_FEEDBACK = 3 };
+enum { CTRL_KEEP = 0, CTRL_ZERO = 1, CTRL_RANDOM = 2, CTRL_FEEDBACK = 3, CTRL_SEQUENCE = 4 };   // CTRL_SEQUENCE: mjb_rollout_ctrl only
 
 // counters written per environment (int[8])
 enum { CNT_NCON = 0, CNT_NEFC, CNT_NITER, CNT_CON_DROPPED, CNT_EFC_DROPPED, CNT_BADQPOS, CNT_BADQVEL, CNT_BADQACC, CNT_N };
@@ -169,6 +169,10 @@ struct StepArgs {
                          // further chunk takes HALF of what is left (guided taper down to single steps: the launch's tail is half of the
                          // LAST chunk); nchunk = all chunks.  chunk_plan() below is the one definition, used by host and device.
   const unsigned char* env_mask;   // forward mode (mjb_forward_envs): [batch] bytes, 0 = leave that environment alone; nullptr = all
+  // CTRL_SEQUENCE (mjb_rollout_ctrl): at launch step s environment env applies ctrl[i] = ctrl_seq[s * ctrl_step_stride + env * ctrl_env_stride + i],
+  // device memory in the storage dtype TS, strides in elements (>= 0, checked against the allocation on the host)
+  const void* ctrl_seq;
+  long ctrl_step_stride, ctrl_env_stride;
 };
 
 // Chunk k of the plan (nstep, chunk_steps, nuniform): steps [s0, s1).  Host and device.

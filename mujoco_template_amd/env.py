@@ -279,22 +279,25 @@ class Env:
         obs = self._ensure_extractor().gather_device(self.data, out=out)
         return self.gather_observations(obs) if gather else obs
 
-    def rollout(self, nsteps: int, *, obs_every: int = 0, obs_out=None, obs_spec_handle=None, gather: bool = False):
+    def rollout(self, nsteps: int, *, ctrl=None, obs_every: int = 0, obs_out=None, obs_spec_handle=None, gather: bool = False):
         """Advance ``nsteps`` in ONE kernel launch (controller evaluated on the device).
 
         With ``obs_every = k > 0`` the flat observation of every k-th step is written on the GPU
         and returned as a torch tensor ``[nsteps // k, batch, obs_dim]``.  ``obs_spec_handle`` (a device
         ``ObsSpecHandle``) replaces the environment's own observation layout for this call (the CSV recorder's feed).
         ``gather=True`` (sharded environments): the returned block is the all-gathered ``[nsteps // k, GLOBAL batch, obs_dim]``.
+
+        ``ctrl`` (a torch tensor ``[nsteps, nu]`` or ``[batch, nsteps, nu]`` on the GPU, in the data's dtype): an OPEN-LOOP rollout,
+        step ``s`` applies ``ctrl[s]`` / ``ctrl[e, s]`` (``BatchSim.rollout_ctrl``); the controller is not called, whatever it is.
         """
-        mode = self._device_mode()
-        if mode is None:
-            raise ConfigError("Env.rollout needs a device-side controller (ZeroController / RandomCtrlController) or none")
         if nsteps < 1:
             raise ConfigError("Env.rollout(nsteps): nsteps must be >= 1")
+        mode = CTRL_KEEP if ctrl is not None else self._device_mode()
+        if mode is None:
+            raise ConfigError("Env.rollout needs a device-side controller (ZeroController / RandomCtrlController), none, or ctrl=")
         data, sim, ctl = self.data, self.data.sim, self.controller
         data.push_host_edits()
-        if mode == CTRL_FEEDBACK:
+        if ctrl is None and mode == CTRL_FEEDBACK:
             ctl.upload(sim)                                      # gains + optional ctrl noise, once per (controller, sim)
         spec, ring_ptr = None, 0
         if obs_every > 0:
@@ -305,8 +308,11 @@ class Env:
                 obs_out = torch.empty((nsteps // obs_every, data.batch, spec.dim), device=f"cuda:{sim.device}",
                                       dtype=torch.float32 if sim.dtype == "float32" else torch.float64)
             ring_ptr = obs_out.data_ptr()
-        sim.rollout(nsteps, mode, seed=int(getattr(ctl, "seed", 0)), step0=self._device_steps,
-                    ctrl_scale=float(getattr(ctl, "scale", 1.0)), obs_spec=spec, obs_out_ptr=ring_ptr, obs_every=obs_every)
+        if ctrl is not None:
+            sim.rollout_ctrl(nsteps, ctrl, obs_spec=spec, obs_out_ptr=ring_ptr, obs_every=obs_every)
+        else:
+            sim.rollout(nsteps, mode, seed=int(getattr(ctl, "seed", 0)), step0=self._device_steps,
+                        ctrl_scale=float(getattr(ctl, "scale", 1.0)), obs_spec=spec, obs_out_ptr=ring_ptr, obs_every=obs_every)
         self._device_steps += nsteps
         self._substep += nsteps
         if hasattr(ctl, "step_count"):
