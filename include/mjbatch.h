@@ -197,6 +197,56 @@ int mjb_rollout(mjbData* d, int nstep, int ctrl_mode, unsigned seed, unsigned st
 int mjb_rollout_ctrl(mjbData* d, int nstep, const void* ctrl_dev, long step_stride, long env_stride,
                      const mjbObsSpec* spec, void* obs_out_dev, int obs_every);
 
+/* ---- per-environment model parameters (domain randomisation): these fields may differ between the environments of one data object.
+ * Each is stored as [batch, n] float64 on the data's device (plus an fp32 copy, (float)double, for float32 data); every kernel that
+ * runs environment e's physics (step in both work maps, two-wave step, forward / forward_envs / inverse, host-driven steps, rollouts,
+ * finite differences, Jacobians) reads e's row of a batched field and the model table of the others.
+ *   name               n per environment   bit of the mask
+ *   body_mass          nbody               0 (MJB_PRM_BODY_MASS)
+ *   body_inertia       nbody * 3           1
+ *   dof_damping        nv                  2
+ *   dof_armature       nv                  3
+ *   actuator_gear      nu * 6              4
+ *   actuator_gainprm   nu * 3              5
+ *   actuator_biasprm   nu * 3              6
+ *   geom_friction      ngeom * 3           7
+ *   gravity            3                   8
+ * Semantics: those of MuJoCo when a field of mjModel is edited without mj_setConst.  Per environment the library re-derives only what
+ * the compiler derives from these fields, the same way: body_subtreemass = sum of body_mass over the subtree, and the friction of a
+ * collision pair = element-wise max of its two geoms' friction, stored [f0, f0, f1, f2, f2].  body_invweight0, dof_invweight0,
+ * meaninertia, the pair's translational invweight term and every constraint K / B constant stay those of the compiled model.
+ * Batching dof_damping on a model whose compiled damping is all zero switches that data's Euler step to the implicit-damping path.
+ * Parameters are model, not state: mjb_reset, mjb_reset_envs and the ticket-map hand-over leave them alone.  A specialised kernel is
+ * built for one set of batched fields (its source defines MJB_SPEC_PARAMS when the set is not empty): a call that changes the set
+ * unloads the specialised kernels built for another set (the generic kernels run until the caller loads new ones), and
+ * mjb_kernel_load rejects a code object built for another set with MJB_ERR_ARG. ---- */
+#define MJB_PRM_BODY_MASS 0
+#define MJB_PRM_BODY_INERTIA 1
+#define MJB_PRM_DOF_DAMPING 2
+#define MJB_PRM_DOF_ARMATURE 3
+#define MJB_PRM_ACTUATOR_GEAR 4
+#define MJB_PRM_ACTUATOR_GAINPRM 5
+#define MJB_PRM_ACTUATOR_BIASPRM 6
+#define MJB_PRM_GEOM_FRICTION 7
+#define MJB_PRM_GRAVITY 8
+#define MJB_PRM_N 9
+/* Write the rows of field `name` from src [batch, n] (src_dtype MJB_F32 or MJB_F64; src_on_device = 0: host memory, 1: device memory of
+ * the data's device).  env_mask: optional [batch] bytes in device memory, non-zero = write that environment's row; NULL = every row.
+ * The first call for a field initialises every row to the model's values, so rows outside the mask keep those.  The copy and the
+ * re-derivation of body_subtreemass / pair friction run on the data's stream (a small kernel), behind the launches already queued;
+ * host memory is read before the call returns.  MJB_ERR_ARG: unknown name; host values that are not finite; src or env_mask not
+ * device memory of the data's device, or the allocation behind it shorter than batch * n elements / batch bytes
+ * (hipPointerGetAttributes / hipMemGetAddressRange, as for mjb_rollout_ctrl's table). */
+int mjb_set_env_param(mjbData* d, const char* name, const void* src, int src_dtype, int src_on_device, const unsigned char* env_mask);
+/* host_out [batch, n] float64: the rows of a batched field, or the model's values broadcast to every environment.  Synchronises. */
+int mjb_get_env_param(mjbData* d, const char* name, double* host_out);
+/* Return field `name` to the shared model value for every environment (frees its rows after the stream has drained). */
+int mjb_clear_env_param(mjbData* d, const char* name);
+/* *mask = the batched fields, bit MJB_PRM_* per field. */
+int mjb_env_param_mask(mjbData* d, int* mask);
+/* mjb_model_kernel_source for a data object whose batched fields are `params_mask` (bits MJB_PRM_*); mask 0 gives the same text. */
+long mjb_model_kernel_source_params(mjbModel* m, int kind, int dtype, int lanes, int nconmax, int nefcmax, int params_mask, char* buf, long cap);
+
 /* gains of MJB_CTRL_FEEDBACK, host float64: K [nu, 2nv] row-major, u0 [nu], q0 [nq], v0 [nv] (NULL = zeros); shared by all environments */
 int mjb_set_feedback(mjbData* d, const double* K, const double* u0, const double* q0, const double* v0);
 

@@ -79,6 +79,12 @@ def load_library() -> ctypes.CDLL:
     L.mjb_kernel_source.restype = cl
     L.mjb_kernel_load.argtypes = [vp, ci, ctypes.c_char_p, cl]
     L.mjb_kernel_unload.argtypes = [vp, ci]
+    L.mjb_model_kernel_source_params.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.c_char_p, cl]
+    L.mjb_model_kernel_source_params.restype = cl
+    L.mjb_set_env_param.argtypes = [vp, ctypes.c_char_p, vp, ci, ci, vp]
+    L.mjb_get_env_param.argtypes = [vp, ctypes.c_char_p, vp]
+    L.mjb_clear_env_param.argtypes = [vp, ctypes.c_char_p]
+    L.mjb_env_param_mask.argtypes = [vp, pci]
     L.mjb_inverse.argtypes = [vp]
     L.mjb_step.argtypes = [vp, ci]
     L.mjb_rollout.argtypes = [vp, ci, ci, cu, cu, cd, vp, vp, ci]
@@ -131,7 +137,8 @@ def load_library() -> ctypes.CDLL:
                  "mjb_transition_fd", "mjb_jac", "mjb_debug_forward", "mjb_debug_get", "mjb_model_field", "mjb_model_field_at", "mjb_model_save",
                  "mjb_model_load", "mjb_model_load_xml", "mjb_model_load_xml_string", "mjb_integrate_pos", "mjb_differentiate_pos", "mjb_host_view", "mjb_sync_to_host", "mjb_sync_to_device",
                  "mjb_step_host", "mjb_mirror_edited_mask", "mjb_mirror_commit", "mjb_step_host_auto", "mjb_engine_flags",
-                 "mjb_reset_envs", "mjb_forward_envs", "mjb_engine_flags_peek"):
+                 "mjb_reset_envs", "mjb_forward_envs", "mjb_engine_flags_peek", "mjb_set_env_param", "mjb_get_env_param", "mjb_clear_env_param",
+                 "mjb_env_param_mask"):
         getattr(L, name).restype = ci
     _LIB = L
     return L
@@ -319,6 +326,31 @@ class ObsSpecHandle:
 
 MIRROR_FIELDS = ("qpos", "qvel", "ctrl", "qacc", "qacc_warmstart", "time")     # bit order of the field masks of mjb_sync_to_device / mjb_step_host
 
+# model fields that may differ per environment (mjb_set_env_param), in the bit order of the C masks (MJB_PRM_*)
+ENV_PARAM_FIELDS = ("body_mass", "body_inertia", "dof_damping", "dof_armature", "actuator_gear", "actuator_gainprm", "actuator_biasprm",
+                    "geom_friction", "gravity")
+
+
+def env_param_shape(compiled: CompiledModel, name: str) -> tuple[int, ...]:
+    """Per-environment shape of a field of ``ENV_PARAM_FIELDS``."""
+    m = compiled
+    shapes = {"body_mass": (m.nbody,), "body_inertia": (m.nbody, 3), "dof_damping": (m.nv,), "dof_armature": (m.nv,),
+              "actuator_gear": (m.nu, 6), "actuator_gainprm": (m.nu, 3), "actuator_biasprm": (m.nu, 3), "geom_friction": (m.ngeom, 3),
+              "gravity": (3,)}
+    if name not in shapes:
+        raise ConfigError(f"{name!r} is not a per-environment model field (one of {', '.join(ENV_PARAM_FIELDS)})")
+    return shapes[name]
+
+
+def env_param_mask(params) -> int:
+    """Bit mask (MJB_PRM_*) of a collection of field names."""
+    mask = 0
+    for name in params:
+        if name not in ENV_PARAM_FIELDS:
+            raise ConfigError(f"{name!r} is not a per-environment model field (one of {', '.join(ENV_PARAM_FIELDS)})")
+        mask |= 1 << ENV_PARAM_FIELDS.index(name)
+    return mask
+
 
 class DeviceModel:
     """Handle of ``mjbModel`` (host copy of the compiled model inside the library)."""
@@ -410,23 +442,25 @@ class DeviceModel:
     def set_solver(self, iterations: int, tolerance: float) -> None:
         _check(load_library().mjb_model_set_solver(self.ptr, int(iterations), float(tolerance)))
 
-    def _model_source(self, kind: int, dtype: int, lanes: int, nconmax: int, nefcmax: int) -> str:
-        return _source_from(load_library().mjb_model_kernel_source, self.ptr, kind, dtype, int(lanes), int(nconmax), int(nefcmax))
+    def _model_source(self, kind: int, dtype: int, lanes: int, nconmax: int, nefcmax: int, params=()) -> str:
+        return _source_from(load_library().mjb_model_kernel_source_params, self.ptr, kind, dtype, int(lanes), int(nconmax), int(nefcmax),
+                            env_param_mask(params))
 
-    def spec_source(self, *, lanes: int = 0, nconmax: int = 0, nefcmax: int = 0) -> str:
-        """Translation unit of the specialised fp32 step kernel for these creation arguments (no GPU needed)."""
-        return self._model_source(MJB_KERNEL_STEP, MJB_F32, lanes, nconmax, nefcmax)
+    def spec_source(self, *, lanes: int = 0, nconmax: int = 0, nefcmax: int = 0, params=()) -> str:
+        """Translation unit of the specialised fp32 step kernel for these creation arguments (no GPU needed); ``params``: the
+        per-environment fields (``ENV_PARAM_FIELDS``) of the data objects it is for."""
+        return self._model_source(MJB_KERNEL_STEP, MJB_F32, lanes, nconmax, nefcmax, params)
 
-    def step2_spec_source(self, *, lanes: int = 0, nconmax: int = 0, nefcmax: int = 0) -> str | None:
+    def step2_spec_source(self, *, lanes: int = 0, nconmax: int = 0, nefcmax: int = 0, params=()) -> str | None:
         """Translation unit of the specialised two-wave step kernel (small batches), or None when that kernel does not apply."""
         try:
-            return self._model_source(MJB_KERNEL_STEP2, MJB_F32, lanes, nconmax, nefcmax)
+            return self._model_source(MJB_KERNEL_STEP2, MJB_F32, lanes, nconmax, nefcmax, params)
         except TemplateError:
             return None
 
-    def fd_spec_source(self, *, dtype: str = "float32", lanes: int = 0, nconmax: int = 0, nefcmax: int = 0) -> str:
+    def fd_spec_source(self, *, dtype: str = "float32", lanes: int = 0, nconmax: int = 0, nefcmax: int = 0, params=()) -> str:
         """Translation unit of the specialised float64 finite-difference kernel for these creation arguments (no GPU needed)."""
-        return self._model_source(MJB_KERNEL_FD, MJB_F32 if dtype == "float32" else MJB_F64, lanes, nconmax, nefcmax)
+        return self._model_source(MJB_KERNEL_FD, MJB_F32 if dtype == "float32" else MJB_F64, lanes, nconmax, nefcmax, params)
 
     def __del__(self):
         try:
@@ -520,6 +554,93 @@ class BatchSim:
     def unspecialize_fd(self) -> None:
         _check(load_library().mjb_kernel_unload(self.ptr, MJB_KERNEL_FD))
         self.fd_specialized = False
+
+    # -- per-environment model parameters (mjb_set_env_param) -----------------------------------
+    def env_param_mask(self) -> int:
+        out = ctypes.c_int(0)
+        _check(load_library().mjb_env_param_mask(self.ptr, ctypes.byref(out)))
+        return int(out.value)
+
+    def env_param_fields(self) -> tuple[str, ...]:
+        """The fields that are batched on this object."""
+        mask = self.env_param_mask()
+        return tuple(f for k, f in enumerate(ENV_PARAM_FIELDS) if (mask >> k) & 1)
+
+    def _respecialize(self, mask_before: int) -> None:
+        """The library unloads the specialised kernels when the set of batched fields changes: rebuild them for the new set (the
+        kernel source carries the set, so the in-tree cache keeps one code object per set)."""
+        if self.env_param_mask() == mask_before:
+            return
+        if self.specialized:
+            self.specialized = False
+            self._specialize_by_policy(self.specialize, "step kernel", default=True)
+        if self.fd_specialized:
+            self.fd_specialized = False
+            self._specialize_by_policy(self.specialize_fd, "finite-difference kernel", default=True)
+
+    def set_env_params(self, envs=None, **fields) -> None:
+        """Per-environment model parameters (domain randomisation), e.g. ``set_env_params(body_mass=m, gravity=g)``.  Each value is
+        ``[batch, *shape]`` or ``[*shape]`` (broadcast to the rows written), shape as in ``env_param_shape``: a torch tensor on this
+        object's GPU (copied on the device, enqueued on torch's current stream: nothing crosses to the host) or anything numpy takes
+        (host float64, finiteness checked).  ``envs``: the environments whose rows are written, a mask or an index list as for
+        ``reset_envs`` (``None`` = all); the other rows keep their values (the model's, the first time a field is set).  Semantics,
+        derived quantities and what stays the compiled model's: ``include/mjbatch.h`` / INTEGRATION.md."""
+        import torch
+
+        L = load_library()
+        mask_before = self.env_param_mask()
+        m = self.env_mask(envs)
+        self._prm_mask_keep = m
+        dev = torch.device(f"cuda:{self.device}")
+        keep = []
+        try:
+            for name, value in fields.items():
+                shape = env_param_shape(self.model.compiled, name)
+                n = int(np.prod(shape))
+                if isinstance(value, torch.Tensor):
+                    if value.device != dev:
+                        raise ConfigError(f"set_env_params: {name} must live on {dev}, got {value.device}")
+                    if value.dtype not in (torch.float32, torch.float64):
+                        raise ConfigError(f"set_env_params: {name} must be float32 or float64, got {value.dtype}")
+                    if tuple(value.shape) == shape:
+                        value = value.reshape(1, n).expand(self.batch, n)
+                    elif tuple(value.shape) != (self.batch, *shape):
+                        raise ConfigError(f"set_env_params: {name} must have shape {[self.batch, *shape]} or {list(shape)}, got {list(value.shape)}")
+                    value = value.reshape(self.batch, n).contiguous()
+                    keep.append(value)
+                    self.use_torch_stream()
+                    _check(L.mjb_set_env_param(self.ptr, name.encode(), ctypes.c_void_p(value.data_ptr()) if n else None,
+                                               MJB_F32 if value.dtype == torch.float32 else MJB_F64, 1,
+                                               ctypes.c_void_p(m.data_ptr()) if m is not None else None))
+                else:
+                    arr = np.asarray(value, dtype=np.float64)
+                    if arr.shape == shape:
+                        arr = np.broadcast_to(arr.reshape(1, n), (self.batch, n))
+                    elif arr.shape != (self.batch, *shape):
+                        raise ConfigError(f"set_env_params: {name} must have shape {[self.batch, *shape]} or {list(shape)}, got {list(arr.shape)}")
+                    arr = np.ascontiguousarray(arr.reshape(self.batch, n))
+                    if m is not None:
+                        self.use_torch_stream()              # the mask was uploaded on torch's stream
+                    _check(L.mjb_set_env_param(self.ptr, name.encode(), arr.ctypes.data if n else None, MJB_F64, 0,
+                                               ctypes.c_void_p(m.data_ptr()) if m is not None else None))
+        finally:
+            self._prm_keep = keep                                    # alive at least until the next call on this object
+            self._respecialize(mask_before)
+
+    def env_params(self, name: str) -> np.ndarray:
+        """``[batch, *shape]`` float64: the rows of a batched field, or the model's value broadcast (synchronises)."""
+        shape = env_param_shape(self.model.compiled, name)
+        out = np.zeros((self.batch, *shape), dtype=np.float64)
+        _check(load_library().mjb_get_env_param(self.ptr, name.encode(), out.ctypes.data))
+        return out
+
+    def clear_env_params(self, *names: str) -> None:
+        """Return these fields (none given: every batched one) to the shared model value."""
+        mask_before = self.env_param_mask()
+        for name in names or self.env_param_fields():
+            env_param_shape(self.model.compiled, name)
+            _check(load_library().mjb_clear_env_param(self.ptr, name.encode()))
+        self._respecialize(mask_before)
 
     # -- plumbing -----------------------------------------------------------------
     def set_stream(self, stream_handle: int) -> None:
@@ -815,4 +936,4 @@ class BatchSim:
             pass
 
 
-__all__ = ["BatchSim", "DeviceModel", "ObsSpecHandle", "MIRROR_FIELDS", "build_library", "load_library", "CTRL_KEEP", "CTRL_ZERO", "CTRL_RANDOM", "CTRL_FEEDBACK"]
+__all__ = ["BatchSim", "DeviceModel", "ObsSpecHandle", "MIRROR_FIELDS", "ENV_PARAM_FIELDS", "env_param_shape", "build_library", "load_library", "CTRL_KEEP", "CTRL_ZERO", "CTRL_RANDOM", "CTRL_FEEDBACK"]

@@ -131,6 +131,13 @@ struct mjbData {
   unsigned* episode = nullptr;            // [batch] resets per environment by mjb_reset_envs (the episode counter of its noise streams)
   unsigned xfer_timeout = 0;              // ticks of the 100 MHz clock a wave waits for a hand-over (0 = not yet read from MJB_XFER_TIMEOUT_MS)
   int xfer_poison_env = -1;               // test hook MJB_XFER_POISON_ENV (-1 = not yet read)
+  // per-environment model parameters (mjb_set_env_param): rows of slot k (PRM_*, mjb_types.hpp) in float64 and, for float32 data, fp32;
+  // the same pointers sit in df.prm / dd.prm, which the kernels receive
+  double* prm_d[PRM_NSLOT] = {};
+  float* prm_f[PRM_NSLOT] = {};
+  int prm_mask = 0;                       // bit k = field k batched
+  int spec_prm[4] = {0, 0, 0, 0};         // the batched fields each loaded specialised kernel was built for
+  double* prm_stage = nullptr; size_t prm_stage_cap = 0;     // device staging of host-memory sources (float64)
 };
 
 namespace {
@@ -456,7 +463,12 @@ std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max) {
 // Translation unit of a per-model specialised kernel (kind: MJB_KERNEL_*) under configuration c: the structural sizes of DevModel
 // (never the run-time options: disableactuator, iterations, tolerance) and every offset of the kernel's LDS layout become
 // __builtin_assume()s, and the model itself becomes constant data of the translation unit.
-std::string spec_source(const HostModel& h, const Config& c, int dtype, int kind) {
+std::string spec_source(const HostModel& h_model, const Config& c, int dtype, int kind, int prm_mask) {
+  // per-environment damping makes the implicit-damping path part of the step (mjb_device.hpp has_damping): the kernel is built, and the
+  // model baked, as for a model with damping
+  HostModel h_damped;
+  if ((prm_mask >> PRM_DOF_DAMPING) & 1) { h_damped = h_model; h_damped.has_damping = 1; }
+  const HostModel& h = (prm_mask >> PRM_DOF_DAMPING) & 1 ? h_damped : h_model;
   const KernelTarget t = kernel_target(c, dtype, kind);
   const Lay& L = *t.L;
   const int ncon_max = c.ncon_max, nefc_max = c.nefc_max;
@@ -470,7 +482,9 @@ std::string spec_source(const HostModel& h, const Config& c, int dtype, int kind
   SM(nvp, h.nvp); SM(nvshift, h.nvshift); SM(ncon_max, ncon_max); SM(nefc_max, nefc_max); SM(nsiteact, h.siteact.size()); SM(nmpair, h.mpair.size());
   SM(nround, h.nround); SM(nround_inner, h.nround_inner); SM(max_nsub, h.max_nsub); SM(dfs_ok, h.dfs_ok);
 #undef SM
-  s += "\n#define MJB_SPEC_ASSUME_LAY(L)";
+  s += "\n";
+  if (prm_mask) s += "#define MJB_SPEC_PARAMS " + std::to_string(prm_mask) + "   // per-environment model parameters: bit k = field MJB_PRM_k\n";
+  s += "#define MJB_SPEC_ASSUME_LAY(L)";
 #define SL(f) A("L", #f, (long)L.f)
   SL(qpos); SL(qvel); SL(ctrl); SL(qacc); SL(qacc_ws); SL(qacc_smooth); SL(qfrc_bias); SL(qfrc_passive); SL(qfrc_actuator); SL(qfrc_smooth);
   SL(qfrc_constraint); SL(xpos); SL(xquat); SL(xmat); SL(xipos); SL(ximat); SL(xanchor); SL(xaxis); SL(geom_xpos); SL(geom_xmat); SL(site_xpos);
@@ -492,6 +506,7 @@ std::string spec_source(const HostModel& h, const Config& c, int dtype, int kind
   }
   s += kind != MJB_KERNEL_FD ? baked_model_source<float>(h, ncon_max, nefc_max) : baked_model_source<double>(h, ncon_max, nefc_max);
   s += "#include \"mjb_kernels.hpp\"\n";
+  if (prm_mask) s += "extern \"C\" __constant__ int mjb_spec_params = " + std::to_string(prm_mask) + ";   // checked by mjb_kernel_load\n";
   return s;
 }
 
@@ -751,6 +766,8 @@ void mjb_data_free(mjbData* d) {
   if (d->io_pin) (void)hipHostFree(d->io_pin);
   if (d->flags_pin) (void)hipHostFree(d->flags_pin);
   for (int k = 0; k < 2; k++) { if (d->jac_pin[k]) (void)hipHostFree(d->jac_pin[k]); if (d->jac_dev[k]) (void)hipFree(d->jac_dev[k]); }
+  for (int k = 0; k < PRM_NSLOT; k++) { if (d->prm_d[k]) (void)hipFree(d->prm_d[k]); if (d->prm_f[k]) (void)hipFree(d->prm_f[k]); }
+  if (d->prm_stage) (void)hipFree(d->prm_stage);
   d->alloc.release();
   delete d;
 }
@@ -890,25 +907,30 @@ static StepArgs make_args(mjbData* d, int nstep, int ctrl_mode, unsigned seed, u
 }
 
 // the specialised kernels: model-level and data-level sources come from the same configuration (derive_config) and the same target
-static long kernel_source(const HostModel& h, const Config& c, int dtype, int kind, char* buf, long cap) {
+static long kernel_source(const HostModel& h, const Config& c, int dtype, int kind, int prm_mask, char* buf, long cap) {
   if (check_kind(c, dtype, kind) != MJB_OK) return -1;
-  const std::string src = spec_source(h, c, dtype, kind);
+  if (prm_mask < 0 || prm_mask >= (1 << PRM_NFIELD)) { fail(MJB_ERR_ARG, "params_mask has bits beyond MJB_PRM_N"); return -1; }
+  const std::string src = spec_source(h, c, dtype, kind, prm_mask);
   if (buf && cap > (long)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
   return (long)src.size();
 }
 
-long mjb_model_kernel_source(mjbModel* m, int kind, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap) {
+long mjb_model_kernel_source_params(mjbModel* m, int kind, int dtype, int lanes, int nconmax, int nefcmax, int params_mask, char* buf, long cap) {
   if (!m) { fail(MJB_ERR_ARG, "model is NULL"); return -1; }
   if (dtype != MJB_F32 && dtype != MJB_F64) { fail(MJB_ERR_ARG, "dtype must be MJB_F32 or MJB_F64"); return -1; }
   Config c;
   std::string err;
   if (!derive_config(m->h, dtype, lanes, nconmax, nefcmax, c, err)) { fail(MJB_ERR_ARG, err); return -1; }
-  return kernel_source(m->h, c, dtype, kind, buf, cap);
+  return kernel_source(m->h, c, dtype, kind, params_mask, buf, cap);
+}
+
+long mjb_model_kernel_source(mjbModel* m, int kind, int dtype, int lanes, int nconmax, int nefcmax, char* buf, long cap) {
+  return mjb_model_kernel_source_params(m, kind, dtype, lanes, nconmax, nefcmax, 0, buf, cap);
 }
 
 long mjb_kernel_source(mjbData* d, int kind, char* buf, long cap) {
   if (!d) { fail(MJB_ERR_ARG, "data is NULL"); return -1; }
-  return kernel_source(d->model->h, d->cfg, d->dtype, kind, buf, cap);
+  return kernel_source(d->model->h, d->cfg, d->dtype, kind, d->prm_mask, buf, cap);
 }
 
 // Unload a kind's module (after the stream has drained).  The step kernel's occupancy decides the ticket map's grid: re-query it.
@@ -931,7 +953,19 @@ int mjb_kernel_load(mjbData* d, int kind, const void* image, long nbytes) {
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("hipModuleLoadData: ") + hipGetErrorString(e));
   e = hipModuleGetFunction(&fn, mod, kKinds[kind].symbol);
   if (e != hipSuccess) { (void)hipModuleUnload(mod); return fail(MJB_ERR_DEVICE, std::string("code object has no ") + kKinds[kind].symbol + " kernel"); }
-  d->spec[kind].mod = mod; d->spec[kind].fn = fn;
+  // the batched fields the kernel was built for (spec_source: the symbol exists when the set is not empty) must be this data's: a
+  // kernel built for a field reads only that field's rows, one built without it reads only the model table
+  int built_for = 0;
+  hipDeviceptr_t sym = nullptr; size_t symsize = 0;
+  if (hipModuleGetGlobal(&sym, &symsize, mod, "mjb_spec_params") == hipSuccess && symsize == sizeof(int)) {
+    if (hipMemcpyDtoH(&built_for, sym, sizeof(int)) != hipSuccess) { (void)hipModuleUnload(mod); return fail(MJB_ERR_DEVICE, "reading mjb_spec_params of the code object failed"); }
+  } else (void)hipGetLastError();
+  if (built_for != d->prm_mask) {
+    (void)hipModuleUnload(mod);
+    return fail(MJB_ERR_ARG, "the specialised kernel was built for per-environment parameters " + std::to_string(built_for) + ", this data object has " +
+                                 std::to_string(d->prm_mask) + " (take the source from mjb_kernel_source after mjb_set_env_param)");
+  }
+  d->spec[kind].mod = mod; d->spec[kind].fn = fn; d->spec_prm[kind] = built_for;
   if (kind == MJB_KERNEL_STEP) d->step_slots = -1;
   return MJB_OK;
 }
@@ -1036,6 +1070,259 @@ int mjb_rollout_ctrl(mjbData* d, int nstep, const void* ctrl_dev, long step_stri
   ObsSpecDev obs; std::memset(&obs, 0, sizeof(obs));
   if (spec && obs_out_dev && obs_every > 0) { obs = spec->dev; a.obs_every = obs_every; }
   return launch(d, a, obs, obs_out_dev, false);
+}
+
+}  // extern "C"
+
+// ---- per-environment model parameters (mjb_set_env_param) ----
+namespace {
+static_assert(PRM_BODY_MASS == MJB_PRM_BODY_MASS && PRM_BODY_INERTIA == MJB_PRM_BODY_INERTIA && PRM_DOF_DAMPING == MJB_PRM_DOF_DAMPING &&
+              PRM_DOF_ARMATURE == MJB_PRM_DOF_ARMATURE && PRM_ACT_GEAR == MJB_PRM_ACTUATOR_GEAR && PRM_ACT_GAINPRM == MJB_PRM_ACTUATOR_GAINPRM &&
+              PRM_ACT_BIASPRM == MJB_PRM_ACTUATOR_BIASPRM && PRM_GEOM_FRICTION == MJB_PRM_GEOM_FRICTION && PRM_GRAVITY == MJB_PRM_GRAVITY &&
+              PRM_NFIELD == MJB_PRM_N, "mjbatch.h and mjb_types.hpp number the per-environment fields alike");
+const char* const kPrmNames[PRM_NFIELD] = {"body_mass", "body_inertia", "dof_damping", "dof_armature", "actuator_gear", "actuator_gainprm",
+                                           "actuator_biasprm", "geom_friction", "gravity"};
+
+int prm_index(const char* name) {
+  if (name) for (int k = 0; k < PRM_NFIELD; k++) if (!std::strcmp(name, kPrmNames[k])) return k;
+  return -1;
+}
+// values per environment of slot k (the derived slots included)
+long prm_count(const HostModel& h, int k) {
+  switch (k) {
+    case PRM_BODY_MASS: case PRM_SUBTREEMASS: return h.nbody;
+    case PRM_BODY_INERTIA: return 3L * h.nbody;
+    case PRM_DOF_DAMPING: case PRM_DOF_ARMATURE: return h.nv;
+    case PRM_ACT_GEAR: return 6L * h.nu;
+    case PRM_ACT_GAINPRM: case PRM_ACT_BIASPRM: return 3L * h.nu;
+    case PRM_GEOM_FRICTION: return 3L * h.ngeom;
+    case PRM_GRAVITY: return 3;
+    default: return 5L * h.npair;                                      // PRM_PAIR_FRICTION
+  }
+}
+// the compiled model's values of slot k (geom_friction only lives in the model table: the kernels read the pairs' friction)
+bool prm_model_values(const mjbModel* m, int k, std::vector<double>& out, std::string& err) {
+  const HostModel& h = m->h;
+  const long n = prm_count(h, k);
+  static const char* const derived[2] = {"body_subtreemass", "pair_friction"};
+  if (k == PRM_GRAVITY) { out.assign(h.gravity, h.gravity + 3); return true; }
+  if (k == PRM_GEOM_FRICTION) {
+    for (const auto& f : m->fields)
+      if (f.name == "geom_friction" && f.dtype == 0 && f.count == n) {
+        const double* p = (const double*)(m->blob.data() + f.off);
+        out.assign(p, p + n);
+        return true;
+      }
+    err = "geom_friction: the model table has no float64 geom_friction [ngeom, 3]";
+    return false;
+  }
+  out = h.D(k >= PRM_NFIELD ? derived[k - PRM_NFIELD] : kPrmNames[k]);
+  if ((long)out.size() != n) { err = std::string("model field ") + kPrmNames[k < PRM_NFIELD ? k : 0] + " has the wrong size"; return false; }
+  return true;
+}
+
+// Device memory the kernels will read at ptr[0 .. bytes): 0 = device memory of the data's device (or pinned host memory mapped for it)
+// with an allocation behind it that covers the extent, 1 = not such memory, 2 = no allocation found, 3 = the extent lies beyond it.
+// The checks of mjb_rollout_ctrl's control table.
+int device_extent(const mjbData* d, const void* ptr, size_t bytes) {
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  hipError_t e = hipPointerGetAttributes(&at, ptr);
+  if (e != hipSuccess) (void)hipGetLastError();
+  const bool dev_mem = e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == d->device;
+  const bool pinned = e == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer == ptr;
+  if (!dev_mem && !pinned) return 1;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr);
+  if (e != hipSuccess) { (void)hipGetLastError(); return 2; }
+  const __int128 end = (__int128)(uintptr_t)ptr + (__int128)bytes, limit = (__int128)(uintptr_t)base + (__int128)size;
+  if ((uintptr_t)ptr < (uintptr_t)base || end > limit) return 3;
+  return 0;
+}
+int extent_error(int why, const std::string& what) {
+  static const char* const msg[4] = {"", " is not device-accessible memory of this data object's device", ": no allocation found behind it",
+                                     ": the allocation behind it is shorter than the data read"};
+  return fail(MJB_ERR_ARG, "mjb_set_env_param: " + what + msg[why]);
+}
+
+// The masked rows of one field from the caller's [batch, n] block (float32 or float64) into the float64 master and the fp32 copy
+// (rounded once from the float64 value, as fill_dev_model rounds the model tables).
+__global__ void k_prm_set(const void* src, int src_f32, long n, int batch, const unsigned char* mask, double* dst, float* dstf) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)batch * n) return;
+  if (mask && !mask[t / n]) return;
+  const double v = src_f32 ? (double)((const float*)src)[t] : ((const double*)src)[t];
+  dst[t] = v;
+  if (dstf) dstf[t] = (float)v;
+}
+// body_subtreemass of the masked environments: one thread per environment, the compiler's order (leaves to the root, ids descending)
+__global__ void k_prm_subtreemass(const double* mass, const int* parent, int nbody, int batch, const unsigned char* mask, double* sub, float* subf) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= batch || (mask && !mask[e])) return;
+  const double* ms = mass + (size_t)e * nbody;
+  double* s = sub + (size_t)e * nbody;
+  for (int b = 0; b < nbody; b++) s[b] = ms[b];
+  for (int b = nbody - 1; b > 0; b--) s[parent[b]] += s[b];
+  if (subf) for (int b = 0; b < nbody; b++) subf[(size_t)e * nbody + b] = (float)s[b];
+}
+// friction of every collision pair of the masked environments: element-wise max of its two geoms', stored [f0, f0, f1, f2, f2]
+__global__ void k_prm_pair_friction(const double* gf, const int* g1, const int* g2, int ngeom, int npair, int batch, const unsigned char* mask,
+                                    double* pf, float* pff) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)batch * npair) return;
+  const int e = (int)(t / npair), p = (int)(t - (long)e * npair);
+  if (mask && !mask[e]) return;
+  const double* a = gf + ((size_t)e * ngeom + g1[p]) * 3;
+  const double* b = gf + ((size_t)e * ngeom + g2[p]) * 3;
+  double f[3];
+  for (int k = 0; k < 3; k++) f[k] = a[k] > b[k] ? a[k] : b[k];
+  const double v[5] = {f[0], f[0], f[1], f[2], f[2]};
+  for (int k = 0; k < 5; k++) {
+    pf[(size_t)t * 5 + k] = v[k];
+    if (pff) pff[(size_t)t * 5 + k] = (float)v[k];
+  }
+}
+
+// the kernels' view of the rows (both DevData, so that a float32 data object's float64 FD kernel finds the masters)
+void prm_publish(mjbData* d) {
+  for (int k = 0; k < PRM_NSLOT; k++) {
+    d->df.prm.d[k] = d->dd.prm.d[k] = (const double MJB_CONST*)d->prm_d[k];
+    d->df.prm.f[k] = d->dd.prm.f[k] = (const float MJB_CONST*)d->prm_f[k];
+  }
+}
+// After the set of batched fields changed: the specialised kernels built for another set are unloaded (the generic kernels read the
+// rows of whatever is batched; a specialised one reads the rows of exactly its own fields and would fault on a missing row).
+int prm_mask_changed(mjbData* d) {
+  bool drain = false;
+  for (int kind = 1; kind < 4; kind++) if (d->spec[kind].mod && d->spec_prm[kind] != d->prm_mask) drain = true;
+  if (!drain) return MJB_OK;
+  HIPCHK(hipStreamSynchronize(d->stream));
+  for (int kind = 1; kind < 4; kind++) if (d->spec[kind].mod && d->spec_prm[kind] != d->prm_mask) drop_kernel(d, kind);
+  return MJB_OK;
+}
+// rows of slot k, allocated and filled with the model's values for every environment
+int prm_alloc(mjbData* d, int k) {
+  if (d->prm_d[k]) return MJB_OK;
+  std::vector<double> v;
+  std::string err;
+  if (!prm_model_values(d->model, k, v, err)) return fail(MJB_ERR_ARG, err);
+  const size_t n = v.size(), total = (size_t)d->batch * n;
+  std::vector<double> rows(total ? total : 1);
+  for (size_t e = 0; e < (size_t)d->batch; e++) std::memcpy(rows.data() + e * n, v.data(), n * sizeof(double));
+  if (hipMalloc(&d->prm_d[k], rows.size() * sizeof(double)) != hipSuccess) { d->prm_d[k] = nullptr; return fail(MJB_ERR_DEVICE, "device allocation of parameter rows failed"); }
+  HIPCHK(hipMemcpy(d->prm_d[k], rows.data(), total * sizeof(double), hipMemcpyHostToDevice));
+  if (d->dtype == MJB_F32) {
+    std::vector<float> rf(rows.begin(), rows.end());
+    if (hipMalloc(&d->prm_f[k], rf.size() * sizeof(float)) != hipSuccess) { d->prm_f[k] = nullptr; return fail(MJB_ERR_DEVICE, "device allocation of parameter rows failed"); }
+    HIPCHK(hipMemcpy(d->prm_f[k], rf.data(), total * sizeof(float), hipMemcpyHostToDevice));
+  }
+  return MJB_OK;
+}
+void prm_free(mjbData* d, int k) {
+  if (d->prm_d[k]) (void)hipFree(d->prm_d[k]);
+  if (d->prm_f[k]) (void)hipFree(d->prm_f[k]);
+  d->prm_d[k] = nullptr; d->prm_f[k] = nullptr;
+}
+int prm_derived(int k) { return k == PRM_BODY_MASS ? PRM_SUBTREEMASS : (k == PRM_GEOM_FRICTION ? PRM_PAIR_FRICTION : -1); }
+}  // namespace
+
+extern "C" {
+
+int mjb_set_env_param(mjbData* d, const char* name, const void* src, int src_dtype, int src_on_device, const unsigned char* env_mask) {
+  if (!d || !src) return fail(MJB_ERR_ARG, "NULL argument");
+  const int k = prm_index(name);
+  if (k < 0) return fail(MJB_ERR_ARG, std::string("mjb_set_env_param: unknown per-environment field '") + (name ? name : "") + "'");
+  if (src_dtype != MJB_F32 && src_dtype != MJB_F64) return fail(MJB_ERR_ARG, "mjb_set_env_param: src_dtype must be MJB_F32 or MJB_F64");
+  const HostModel& h = d->model->h;
+  const long n = prm_count(h, k);
+  const size_t total = (size_t)d->batch * (size_t)n, esize = src_dtype == MJB_F32 ? 4 : 8;
+  HIPCHK(hipSetDevice(d->device));
+  if (env_mask) { int why = device_extent(d, env_mask, (size_t)d->batch); if (why) return extent_error(why, "env_mask"); }
+  if (src_on_device) {
+    if (total) { int why = device_extent(d, src, total * esize); if (why) return extent_error(why, "src"); }
+  } else {
+    for (size_t i = 0; i < total; i++) {
+      const double v = src_dtype == MJB_F32 ? (double)((const float*)src)[i] : ((const double*)src)[i];
+      if (!std::isfinite(v)) return fail(MJB_ERR_ARG, std::string("mjb_set_env_param: ") + name + " has a value that is not finite");
+    }
+  }
+  const int dk = prm_derived(k);
+  int rc = prm_alloc(d, k);
+  if (rc == MJB_OK && dk >= 0) rc = prm_alloc(d, dk);
+  if (rc != MJB_OK) { prm_free(d, k); if (dk >= 0) prm_free(d, dk); return rc; }
+  if (total == 0) { d->prm_mask |= 1 << k; prm_publish(d); return prm_mask_changed(d); }
+  const void* from = src;
+  int from_f32 = src_dtype == MJB_F32;
+  if (!src_on_device) {                                        // host memory: through the pinned block to a device stage, read before return
+    const size_t bytes = total * sizeof(double);
+    rc = ensure_io_pin(d, bytes);
+    if (rc != MJB_OK) return rc;
+    if (d->prm_stage_cap < bytes) {
+      if (d->prm_stage) { HIPCHK(hipStreamSynchronize(d->stream)); (void)hipFree(d->prm_stage); }
+      d->prm_stage = nullptr; d->prm_stage_cap = 0;
+      HIPCHK(hipMalloc(&d->prm_stage, bytes));
+      d->prm_stage_cap = bytes;
+    }
+    double* pin = (double*)d->io_pin;
+    for (size_t i = 0; i < total; i++) pin[i] = src_dtype == MJB_F32 ? (double)((const float*)src)[i] : ((const double*)src)[i];
+    HIPCHK(hipMemcpyAsync(d->prm_stage, pin, bytes, hipMemcpyHostToDevice, d->stream));
+    from = d->prm_stage; from_f32 = 0;
+  }
+  const int threads = 256;
+  hipLaunchKernelGGL(k_prm_set, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, d->stream, from, from_f32, n, d->batch,
+                     env_mask, d->prm_d[k], d->prm_f[k]);
+  HIPCHK(hipGetLastError());
+  if (k == PRM_BODY_MASS)
+    hipLaunchKernelGGL(k_prm_subtreemass, dim3((unsigned)((d->batch + 63) / 64)), dim3(64), 0, d->stream, d->prm_d[k], d->md.body_parentid, h.nbody,
+                       d->batch, env_mask, d->prm_d[PRM_SUBTREEMASS], d->prm_f[PRM_SUBTREEMASS]);
+  else if (k == PRM_GEOM_FRICTION && h.npair > 0) {
+    const size_t np = (size_t)d->batch * h.npair;
+    hipLaunchKernelGGL(k_prm_pair_friction, dim3((unsigned)((np + threads - 1) / threads)), dim3(threads), 0, d->stream, d->prm_d[k], d->md.pair_geom1,
+                       d->md.pair_geom2, h.ngeom, h.npair, d->batch, env_mask, d->prm_d[PRM_PAIR_FRICTION], d->prm_f[PRM_PAIR_FRICTION]);
+  }
+  HIPCHK(hipGetLastError());
+  if (!src_on_device) HIPCHK(hipStreamSynchronize(d->stream));            // the pinned block is free again on return
+  const int before = d->prm_mask;
+  d->prm_mask |= 1 << k;
+  prm_publish(d);
+  return d->prm_mask != before ? prm_mask_changed(d) : MJB_OK;
+}
+
+int mjb_get_env_param(mjbData* d, const char* name, double* host_out) {
+  if (!d || !host_out) return fail(MJB_ERR_ARG, "NULL argument");
+  const int k = prm_index(name);
+  if (k < 0) return fail(MJB_ERR_ARG, std::string("mjb_get_env_param: unknown per-environment field '") + (name ? name : "") + "'");
+  const long n = prm_count(d->model->h, k);
+  if (!d->prm_d[k]) {
+    std::vector<double> v;
+    std::string err;
+    if (!prm_model_values(d->model, k, v, err)) return fail(MJB_ERR_ARG, err);
+    for (size_t e = 0; e < (size_t)d->batch; e++) std::memcpy(host_out + e * n, v.data(), n * sizeof(double));
+    return MJB_OK;
+  }
+  HIPCHK(hipSetDevice(d->device));
+  return copy_out(d, ArrayInfo{d->prm_d[k], n, 1}, host_out);
+}
+
+int mjb_clear_env_param(mjbData* d, const char* name) {
+  if (!d) return fail(MJB_ERR_ARG, "data is NULL");
+  const int k = prm_index(name);
+  if (k < 0) return fail(MJB_ERR_ARG, std::string("mjb_clear_env_param: unknown per-environment field '") + (name ? name : "") + "'");
+  if (!d->prm_d[k]) return MJB_OK;
+  HIPCHK(hipSetDevice(d->device));
+  HIPCHK(hipStreamSynchronize(d->stream));                     // launches already queued read these rows
+  prm_free(d, k);
+  if (prm_derived(k) >= 0) prm_free(d, prm_derived(k));
+  d->prm_mask &= ~(1 << k);
+  prm_publish(d);
+  return prm_mask_changed(d);
+}
+
+int mjb_env_param_mask(mjbData* d, int* mask) {
+  if (!d || !mask) return fail(MJB_ERR_ARG, "NULL argument");
+  *mask = d->prm_mask;
+  return MJB_OK;
 }
 
 int mjb_set_feedback(mjbData* d, const double* K, const double* u0, const double* q0, const double* v0) {

@@ -571,6 +571,8 @@ template <typename T> struct Ctx {
   bool skip_dynamics = false;   // inverse-dynamics mode: forward() stops before actuation / constraint solve
   const DevModel<T> MJB_CONST* mp;
   const Lay MJB_CONST* lp;
+  const PrmRows MJB_CONST* pr;  // per-environment model parameters of the data (prm_row); null: none (host emulation without data)
+  int env;                      // the environment this context runs: its row of every batched field
   T* w;      // T region of this environment's LDS slice
   int* wi;   // int region
   int lane;
@@ -582,8 +584,72 @@ template <typename T> struct Ctx {
   unsigned long long pacc[PH_N] = {};
   unsigned long long pt = 0;
 #endif
-  MJB_DEVM Ctx(const DevModel<T> MJB_CONST* m_, const Lay MJB_CONST* L_, T* w_, int* wi_, int lane_) : mp(m_), lp(L_), w(w_), wi(wi_), lane(lane_), ncon(0), nefc(0), niter(0), con_dropped(0), efc_dropped(0) {}
+  MJB_DEVM Ctx(const DevModel<T> MJB_CONST* m_, const Lay MJB_CONST* L_, T* w_, int* wi_, int lane_, const PrmRows MJB_CONST* pr_ = nullptr, int env_ = 0)
+      : mp(m_), lp(L_), pr(pr_), env(env_), w(w_), wi(wi_), lane(lane_), ncon(0), nefc(0), niter(0), con_dropped(0), efc_dropped(0) {}
 };
+
+// ---------------------------------------------------------------------------
+// Per-environment model parameters (mjb_set_env_param).  prm_row<K>(c, tab, n) is the ONE accessor of field K: the base of the
+// environment's row of that field when it is batched, else the model table `tab` (n values per environment).  The row base is
+// uniform over the environment's lane group and is read through the constant address space like the tables, so a read at a uniform
+// index stays a scalar load.  Generic kernels branch (uniformly) on the slot's pointer.  A specialised translation unit knows its
+// fields: MJB_SPEC_PARAMS (bit K = field K batched; absent = none) - an unbatched field reads its baked table exactly as before, a
+// batched one reads only the rows (no folded constants, no branch).
+// ---------------------------------------------------------------------------
+#if defined(MJB_SPEC_KERNEL) && !defined(MJB_HOST_EMU)
+#ifndef MJB_SPEC_PARAMS
+#define MJB_SPEC_PARAMS 0
+#endif
+#define MJB_PRM_ON(k) ((((MJB_SPEC_PARAMS) >> (k)) & 1) != 0)
+#define MJB_PRM_SURE 1
+#else
+#define MJB_PRM_ON(k) true
+#define MJB_PRM_SURE 0
+#endif
+// the derived slots follow their source field (PrmRows)
+template <int K> MJB_DEVM constexpr int prm_src() { return K == PRM_SUBTREEMASS ? PRM_BODY_MASS : (K == PRM_PAIR_FRICTION ? PRM_GEOM_FRICTION : K); }
+template <typename T> struct PrmSel;
+template <> struct PrmSel<float> { static MJB_DEVM const float MJB_CONST* get(const PrmRows MJB_CONST* r, int k) { return r->f[k]; } };
+template <> struct PrmSel<double> { static MJB_DEVM const double MJB_CONST* get(const PrmRows MJB_CONST* r, int k) { return r->d[k]; } };
+template <int K, typename T, typename TP>
+MJB_DEV const T MJB_CONST* prm_row(const Ctx<T>& c, TP tab, int n) {
+  if constexpr (MJB_PRM_ON(prm_src<K>())) {
+#ifdef MJB_HOST_EMU
+    if (!c.pr) return tab;
+#endif
+    const T MJB_CONST* row = PrmSel<T>::get(c.pr, K);
+    if (MJB_PRM_SURE || row) return row + (long)c.env * n;
+  }
+  return tab;
+}
+// value i of field K where the model's value sits at tab[ti] of another table (a record that packs several fields)
+template <int K, typename T, typename TP>
+MJB_DEV T prm_get(const Ctx<T>& c, TP tab, int n, int i, int ti) {
+  if constexpr (MJB_PRM_ON(prm_src<K>())) {
+#ifdef MJB_HOST_EMU
+    if (!c.pr) return tab[ti];
+#endif
+    const T MJB_CONST* row = PrmSel<T>::get(c.pr, K);
+    if (MJB_PRM_SURE || row) return row[(long)c.env * n + i];
+  }
+  return tab[ti];
+}
+// has_damping of this data: the model's, or per-environment damping (then the implicit-damping path runs for every environment)
+template <typename T> MJB_DEV bool has_damping(const Ctx<T>& c, int model_has_damping) {
+  if constexpr (MJB_PRM_ON(PRM_DOF_DAMPING)) {
+    if (MJB_PRM_SURE) return true;
+#ifdef MJB_HOST_EMU
+    if (!c.pr) return model_has_damping != 0;
+#endif
+    return model_has_damping != 0 || PrmSel<T>::get(c.pr, PRM_DOF_DAMPING) != nullptr;
+  }
+  return model_has_damping != 0;
+}
+// what the factorisations read of the model in mode 2 (A = M + h diag(damping)): the timestep and the environment's damping row
+template <typename T> struct DampRef { T timestep; const T MJB_CONST* dof_damping; };
+template <typename T> MJB_DEV DampRef<T> damp_ref(const Ctx<T>& c, const DevModel<T> MJB_CONST& m) {
+  return DampRef<T>{m.timestep, prm_row<PRM_DOF_DAMPING>(c, m.dof_damping, m.nv)};
+}
 
 // ---------------------------------------------------------------------------
 // Hooks of the diagnostic builds, all of them no-ops in the product kernel:
@@ -1026,16 +1092,17 @@ template <typename T, int G> MJB_DEV void factor_W_impl(Ctx<T>& c, int mode, T* 
       // the backward-stable Cholesky, whose packed factor in W is reused while the active set does not change.
       if constexpr (sizeof(T) == 4) {
         unsigned long long* pf = MJB_PACC(c, PH_FAC_LOAD);
-        if (mode != 1) mfma_sweep_solve32<ModelRef<T>>(m, M, w + L.tmp, J, dw, nefc, mode, nv, lane, x, pf);
-        else mfma_factor32<ModelRef<T>>(m, M, W, w + L.tmp, w + L.cholcol, J, dw, nefc, mode, nv, lane, x, pf);
-      } else reg_factor32<T, ModelRef<T>>(m, M, W, w + L.tmp, J, dw, nefc, mode, nv, lane, x);
+        if (mode != 1) mfma_sweep_solve32<DampRef<T>>(damp_ref(c, m), M, w + L.tmp, J, dw, nefc, mode, nv, lane, x, pf);
+        else mfma_factor32<DampRef<T>>(damp_ref(c, m), M, W, w + L.tmp, w + L.cholcol, J, dw, nefc, mode, nv, lane, x, pf);
+      } else reg_factor32<T, DampRef<T>>(damp_ref(c, m), M, W, w + L.tmp, J, dw, nefc, mode, nv, lane, x);
       return;
     }
-    tile_factor<T, 8, ModelRef<T>>(m, M, W, w + L.tmp, w + L.cholcol, J, dw, nefc, mode, nv, lane);
+    tile_factor<T, 8, DampRef<T>>(damp_ref(c, m), M, W, w + L.tmp, w + L.cholcol, J, dw, nefc, mode, nv, lane);
     if (x) chol_solve<T, G>(W, w + L.tmp, x, nv, lane);
     return;
   }
   int np = nv * (nv + 1) / 2;
+  const T MJB_CONST* damping = prm_row<PRM_DOF_DAMPING>(c, m.dof_damping, nv);
   for (int idx = lane; idx < np; idx += G) {
     int i, k;
     tri_rc(m.tri_tab, idx, i, k);
@@ -1045,7 +1112,7 @@ template <typename T, int G> MJB_DEV void factor_W_impl(Ctx<T>& c, int mode, T* 
         T d = dw[r];
         if (d != 0) h += d * J[r * nv + i] * J[r * nv + k];
       }
-    } else if (mode == 2 && i == k) h += m.timestep * m.dof_damping[i];
+    } else if (mode == 2 && i == k) h += m.timestep * damping[i];
     W[tri_at(i, k)] = h;
   }
   gsync<G>();
@@ -1376,14 +1443,14 @@ template <typename T, int G> MJB_DEV void com_pos(Ctx<T>& c) {
   MJB_ENV(c); T* w = c.w; const int lane = c.lane;
   T *sc = w + L.subtree_com, *xipos = w + L.xipos, *ximat = w + L.ximat, *xmat = w + L.xmat;
   for (int b = lane; b < m.nbody; b += G) {
-    T ms = m.body_mass[b];
+    T ms = prm_row<PRM_BODY_MASS>(c, m.body_mass, m.nbody)[b];
 #pragma unroll
     for (int k = 0; k < 3; k++) sc[3 * b + k] = ms * xipos[3 * b + k];
   }
   gsync<G>();
   tree_backward_sum<T, G, 3>(c, sc, m.nround, 0);           // includes the world body's subtree (everything)
   for (int b = lane; b < m.nbody; b += G) {
-    T sm = m.body_subtreemass[b];
+    T sm = prm_row<PRM_SUBTREEMASS>(c, m.body_subtreemass, m.nbody)[b];
     if (sm < Num<T>::minval()) { sc[3 * b] = xipos[3 * b]; sc[3 * b + 1] = xipos[3 * b + 1]; sc[3 * b + 2] = xipos[3 * b + 2]; }
     else { T inv = 1 / sm; sc[3 * b] *= inv; sc[3 * b + 1] *= inv; sc[3 * b + 2] *= inv; }
   }
@@ -1397,12 +1464,13 @@ template <typename T, int G> MJB_DEV void com_pos(Ctx<T>& c) {
     }
     int r = m.body_rootid[b];
     T off[3], im[9], res[10];
-    T inr[3] = {m.body_inertia[3 * b], m.body_inertia[3 * b + 1], m.body_inertia[3 * b + 2]};
+    const T MJB_CONST* inertia = prm_row<PRM_BODY_INERTIA>(c, m.body_inertia, 3 * m.nbody);
+    T inr[3] = {inertia[3 * b], inertia[3 * b + 1], inertia[3 * b + 2]};
 #pragma unroll
     for (int k = 0; k < 3; k++) off[k] = xipos[3 * b + k] - sc[3 * r + k];
 #pragma unroll
     for (int k = 0; k < 9; k++) im[k] = ximat[9 * b + k];
-    inert_com(res, inr, im, off, m.body_mass[b]);
+    inert_com(res, inr, im, off, prm_row<PRM_BODY_MASS>(c, m.body_mass, m.nbody)[b]);
 #pragma unroll
     for (int k = 0; k < 10; k++) cin[10 * b + k] = res[k];
   }
@@ -1486,7 +1554,7 @@ template <typename T, int G> MJB_DEV void crb_factor(Ctx<T>& c) {
     T val = 0;
 #pragma unroll
     for (int k = 0; k < 6; k++) val += cdof[6 * j + k] * buf[6 * i + k];
-    if (i == j) val += m.dof_armature[i];
+    if (i == j) val += prm_row<PRM_DOF_ARMATURE>(c, m.dof_armature, nv)[i];
     M[i * nv + j] = val; M[j * nv + i] = val;
   }
   gsync<G>();     // M stays unfactored here: it is factored together with the M^-1 solve in actuation_acceleration
@@ -1650,7 +1718,7 @@ template <typename T, int G> MJB_DEV void collide_pass(Ctx<T>& c, int p, bool va
           o[0] = r.dist; o[1] = r.pos[0]; o[2] = r.pos[1]; o[3] = r.pos[2];
 #pragma unroll
           for (int a = 0; a < 6; a++) o[4 + a] = f[a];
-          o[10] = m.pair_friction[5 * p];
+          o[10] = prm_row<PRM_PAIR_FRICTION>(c, m.pair_friction, 5 * m.npair)[5 * p];
           con_pair[slot] = p;
         }
       }
@@ -1925,7 +1993,8 @@ template <typename T, int G> MJB_DEV void vel_bias_passive(Ctx<T>& c) {
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 6; k++) { cvel[k] = 0; cfrc[k] = 0; }
-    cacc[0] = cacc[1] = cacc[2] = 0; cacc[3] = -m.gravity[0]; cacc[4] = -m.gravity[1]; cacc[5] = -m.gravity[2];
+    const T MJB_CONST* gravity = prm_row<PRM_GRAVITY>(c, m.gravity, 3);
+    cacc[0] = cacc[1] = cacc[2] = 0; cacc[3] = -gravity[0]; cacc[4] = -gravity[1]; cacc[5] = -gravity[2];
   }
   gsync<G>();
   // Spatial velocities / bias accelerations are sums over the ancestor dofs (everything is expressed at the subtree COM of
@@ -2004,11 +2073,12 @@ template <typename T, int G> MJB_DEV void vel_bias_passive(Ctx<T>& c) {
   if (m.has_fluid) {
     T *xipos = w + L.xipos, *ximat = w + L.ximat, *sc = w + L.subtree_com;
     for (int b = lane; b < m.nbody; b += G) {
-      T mass = m.body_mass[b];
+      T mass = prm_row<PRM_BODY_MASS>(c, m.body_mass, m.nbody)[b];
 #pragma unroll
       for (int k = 0; k < 6; k++) bfrc[6 * b + k] = 0;
       if (b == 0 || mass < Num<T>::minval()) continue;
-      T I0 = m.body_inertia[3 * b], I1 = m.body_inertia[3 * b + 1], I2 = m.body_inertia[3 * b + 2];
+      const T MJB_CONST* inertia = prm_row<PRM_BODY_INERTIA>(c, m.body_inertia, 3 * m.nbody);
+      T I0 = inertia[3 * b], I1 = inertia[3 * b + 1], I2 = inertia[3 * b + 2];
       T box[3] = {t_sqrt(t_max(Num<T>::minval(), I1 + I2 - I0) / mass * 6), t_sqrt(t_max(Num<T>::minval(), I0 + I2 - I1) / mass * 6), t_sqrt(t_max(Num<T>::minval(), I0 + I1 - I2) / mass * 6)};
       int r = m.body_rootid[b];
       T cv[6], off[3], lin[3], t[3], im[9], lvel[6], lfrc[6] = {0, 0, 0, 0, 0, 0};
@@ -2051,7 +2121,7 @@ template <typename T, int G> MJB_DEV void vel_bias_passive(Ctx<T>& c) {
 #pragma unroll
     for (int k = 0; k < 6; k++) v += cdof[6 * i + k] * cfrc[6 * b + k];
     qb[i] = v;
-    T pf = -m.dof_frec[4 * i] * qvel[i];
+    T pf = -prm_get<PRM_DOF_DAMPING>(c, m.dof_frec, nv, i, 4 * i) * qvel[i];          // damping: the dof record holds the model's
     if (qa >= 0) pf -= m.dof_frec[4 * i + 1] * (qpos[qa] - m.dof_frec[4 * i + 2]);      // hinge / slide spring
     if (m.has_fluid) {
       T* xipos = w + L.xipos;
@@ -2080,15 +2150,17 @@ template <typename T, int G> MJB_DEV void actuation_forces(Ctx<T>& c) {
     if (!(grp >= 0 && grp < 31 && ((MJB_OPT(c, disableactuator) >> grp) & 1))) {
       T u = ctrl[a];
       if (m.actuator_ctrllimited[a]) u = t_min(t_max(u, m.actuator_ctrlrange[2 * a]), m.actuator_ctrlrange[2 * a + 1]);
-      force = m.actuator_gainprm[3 * a] * u;
+      force = prm_row<PRM_ACT_GAINPRM>(c, m.actuator_gainprm, 3 * m.nu)[3 * a] * u;
       if (m.actuator_biastype[a] == 1) {
         T len = 0, vel = 0;
         if (m.actuator_trntype[a] == TRN_JOINT) {
           int j = m.actuator_trnid[2 * a];
-          len = m.actuator_gear[6 * a] * qpos[m.jnt_qposadr[j]];
-          vel = m.actuator_gear[6 * a] * qvel[m.jnt_dofadr[j]];
+          const T MJB_CONST* gear = prm_row<PRM_ACT_GEAR>(c, m.actuator_gear, 6 * m.nu);
+          len = gear[6 * a] * qpos[m.jnt_qposadr[j]];
+          vel = gear[6 * a] * qvel[m.jnt_dofadr[j]];
         }
-        force += m.actuator_biasprm[3 * a] + m.actuator_biasprm[3 * a + 1] * len + m.actuator_biasprm[3 * a + 2] * vel;
+        const T MJB_CONST* bias = prm_row<PRM_ACT_BIASPRM>(c, m.actuator_biasprm, 3 * m.nu);
+        force += bias[3 * a] + bias[3 * a + 1] * len + bias[3 * a + 2] * vel;
       }
       if (m.actuator_forcelimited[a]) force = t_min(t_max(force, m.actuator_forcerange[2 * a]), m.actuator_forcerange[2 * a + 1]);
     }
@@ -2099,13 +2171,14 @@ template <typename T, int G> MJB_DEV void actuation_forces(Ctx<T>& c) {
   T *sx = w + L.site_xpos, *sm = w + L.site_xmat;
   for (int i = lane; i < nv; i += G) {
     T s = 0;
-    for (int k = m.dofact_adr[i]; k < m.dofact_adr[i + 1]; k++) { int a = m.dofact_act[k]; s += m.actuator_gear[6 * a] * af[a]; }
+    const T MJB_CONST* gear = prm_row<PRM_ACT_GEAR>(c, m.actuator_gear, 6 * m.nu);
+    for (int k = m.dofact_adr[i]; k < m.dofact_adr[i + 1]; k++) { int a = m.dofact_act[k]; s += gear[6 * a] * af[a]; }
     for (int k = 0; k < m.nsiteact; k++) {
       int a = m.siteact[k], id = m.actuator_trnid[2 * a], b = m.site_bodyid[id];
       if (!((m.body_dofmask[b] >> i) & 1ull)) continue;
       T g[6], R[9], f[3], tq[3], pt[3] = {sx[3 * id], sx[3 * id + 1], sx[3 * id + 2]}, jp[3], jr[3];
 #pragma unroll
-      for (int q = 0; q < 6; q++) g[q] = m.actuator_gear[6 * a + q];
+      for (int q = 0; q < 6; q++) g[q] = gear[6 * a + q];
 #pragma unroll
       for (int q = 0; q < 9; q++) R[q] = sm[9 * id + q];
       mulmatvec3(f, R, g);
@@ -2456,7 +2529,7 @@ template <typename T, int G> MJB_DEV void euler(Ctx<T>& c, const mjb_f16v* inv =
   MJB_ENV(c); T* w = c.w; const int lane = c.lane, nv = m.nv;
   T *qacc = w + L.qacc, *qvel = w + L.qvel, *qpos = w + L.qpos, *tmpv = w + L.Mv, *M = w + L.M, *W = w + L.W;
   T h = m.timestep;
-  if (m.has_damping) {
+  if (has_damping(c, m.has_damping)) {
     T *qs = w + L.qfrc_smooth, *qc = w + L.qfrc_constraint;
     if (MJB_REPEATS(c, PH_INTEG)) {                            // the implicit-damping solve twice (right-hand side rebuilt: idempotent)
       for (int i = lane; i < nv; i += G) tmpv[i] = qs[i] + qc[i];
@@ -2596,13 +2669,14 @@ template <typename T, typename TS, int G> MJB_DEV void inverse_dynamics(Ctx<T>& 
   for (int idx = lane; idx < m.nu * nv; idx += G) {
     int a = idx / nv, i = idx - a * nv, id = m.actuator_trnid[2 * a];
     T v = 0;
-    if (m.actuator_trntype[a] == TRN_JOINT) v = (i == m.jnt_dofadr[id]) ? m.actuator_gear[6 * a] : (T)0;
+    const T MJB_CONST* gear = prm_row<PRM_ACT_GEAR>(c, m.actuator_gear, 6 * m.nu);
+    if (m.actuator_trntype[a] == TRN_JOINT) v = (i == m.jnt_dofadr[id]) ? gear[6 * a] : (T)0;
     else {
       int b = m.site_bodyid[id];
       if ((m.body_dofmask[b] >> i) & 1ull) {
         T g[6], R[9], f[3], tq[3], pt[3] = {sx[3 * id], sx[3 * id + 1], sx[3 * id + 2]}, jp[3], jr[3];
 #pragma unroll
-        for (int q = 0; q < 6; q++) g[q] = m.actuator_gear[6 * a + q];
+        for (int q = 0; q < 6; q++) g[q] = gear[6 * a + q];
 #pragma unroll
         for (int q = 0; q < 9; q++) R[q] = sm[9 * id + q];
         mulmatvec3(f, R, g);
@@ -2776,7 +2850,7 @@ template <typename T, typename TS, int G>
 MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, DataRef<TS> d, DebugRef<TS> dbg, ArgsRef a,
                      ObsRef obs, TS* obs_out, T* w, int* wi, int env, int lane, int s_begin, int s_end, unsigned tag_in,
                      unsigned long long* tlacc = nullptr) {
-  Ctx<T> c(mp, lp, w, wi, lane);
+  Ctx<T> c(mp, lp, w, wi, lane, &d.prm, env);
   ModelRef<T> m = MJB_MODEL_OF(mp); LayRef L = *lp;
   MJB_SPEC_ASSUME(m) MJB_SPEC_ASSUME_LAY(L)
   const int nq = m.nq, nv = m.nv, nu = m.nu;
@@ -3003,7 +3077,7 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
 template <typename T, typename TS>
 MJB_DEV void env_run2(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, DataRef<TS> d, ArgsRef a, ObsRef obs, TS* obs_out, T* w, int* wi, int env, int lane, int wv) {
   constexpr int G = 64;
-  Ctx<T> c(mp, lp, w, wi, lane);
+  Ctx<T> c(mp, lp, w, wi, lane, &d.prm, env);
   ModelRef<T> m = MJB_MODEL_OF(mp); LayRef L = *lp;
   MJB_SPEC_ASSUME(m) MJB_SPEC_ASSUME_LAY(L)
   const int nq = m.nq, nv = m.nv, nu = m.nu;
@@ -3064,7 +3138,7 @@ MJB_DEV void env_run2(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, 
       } else {
         vel_bias_passive<T, G>(c);
         while (__hip_atomic_load(mail + 5, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != gen) __builtin_amdgcn_s_sleep(1);
-        invm = mfma_sweep_invert32<ModelRef<T>>(m, w + L.M, w + L.efc_J, w + L.efc_jv, 0, 0, nv, lane);
+        invm = mfma_sweep_invert32<DampRef<T>>(damp_ref(c, m), w + L.M, w + L.efc_J, w + L.efc_jv, 0, 0, nv, lane);
       }
       __syncthreads();
       if (wv == 0) actuation_forces<T, G>(c);
@@ -3077,15 +3151,15 @@ MJB_DEV void env_run2(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, 
         if (m.nsensor > 0) { sensors<T, T, G>(c, w + L.sens); gsync<G>(); }
         const bool bad = pass == 0 && group_bad<T, G>(w + L.qacc, nv, lane);
         if (lane == 0) mail[4] = bad ? 1 : 0;
-      } else if (m.has_damping) {
-        inv = mfma_sweep_invert32<ModelRef<T>>(m, w + L.M, w + L.efc_J, w + L.efc_jv, 0, 2, nv, lane);
+      } else if (has_damping(c, m.has_damping)) {
+        inv = mfma_sweep_invert32<DampRef<T>>(damp_ref(c, m), w + L.M, w + L.efc_J, w + L.efc_jv, 0, 2, nv, lane);
       }
       __syncthreads();
       if (mail[4] == 0) break;
       if (wv == 0) { badqacc++; reset_state<T, G>(c); time = 0; }
       __syncthreads();
     }
-    if (wv == 1) euler<T, G>(c, m.has_damping ? &inv : nullptr);
+    if (wv == 1) euler<T, G>(c, has_damping(c, m.has_damping) ? &inv : nullptr);
     __syncthreads();
     if (wv == 0) {
       time += a.dt;

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "mjb_device.hpp"
 
 namespace mjb {
@@ -150,6 +152,16 @@ namespace mjb {
 //   position jobs (2 nv columns, one each):                            everything
 // (RK4 evaluates the dynamics at four states per step: no sharing.)  Jobs are laid out heaviest first, job-major, so that the
 // long ones start first.  Results are the ones the column-per-group kernel gave: a skipped stage would have recomputed the same numbers.
+// The per-environment parameter rows of a kernel whose argument list starts (mg, lg, DevData d): read through the kernarg segment,
+// so that the rows' base pointers are scalar loads of the constant address space (as in k_step_body)
+template <typename T, typename TS> struct ModelDataKernArgs { const DevModel<T>* mg; const Lay* lg; DevData<TS> d; };
+typedef ModelDataKernArgs<double, double> MdkaDD;
+typedef StepKernArgs<double, double> SkaDD;
+static_assert(offsetof(MdkaDD, d) == offsetof(SkaDD, d) && offsetof(MdkaDD, d) == 2 * sizeof(void*), "the kernels' argument lists start (mg, lg, d)");
+template <typename T, typename TS> MJB_DEV const PrmRows MJB_CONST* kernarg_prm() {
+  return &((const ModelDataKernArgs<T, TS> MJB_CONST*)__builtin_amdgcn_kernarg_segment_ptr())->d.prm;
+}
+
 template <typename T, typename TS, int G>
 MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& d, int ncol, T eps, T* y_out, int* valid, int cv, int cc) {
   extern __shared__ __align__(16) char smem[];
@@ -171,7 +183,7 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
   if (rk4) share = 0;
   T* w = (T*)(smem + (size_t)sub * L.bytes);
   int* wi = (int*)(w + L.nT);
-  Ctx<T> c(mp, lp, w, wi, lane);
+  Ctx<T> c(mp, lp, w, wi, lane, kernarg_prm<T, TS>(), env);
   for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;       // structural zeros of the mass matrix (crb_factor fills the rest)
   const int nstage = rk4 ? 4 : 1;
   for (int it = share > 0 ? -1 : 0; it < cnt; it++) {           // it = -1: the shared stages at the nominal state
@@ -293,8 +305,9 @@ __global__ __launch_bounds__(64) void k_jac(const DevModel<T>* mg, const Lay* lg
   ModelRef<T> m = *mp; LayRef L = *lp;
   T* w = (T*)(smem + (size_t)sub * L.bytes);
   int* wi = (int*)(w + L.nT);
-  Ctx<T> c(mp, lp, w, wi, lane);
+  Ctx<T> c(mp, lp, w, wi, lane, kernarg_prm<T, TS>(), env);
   const int nq = m.nq, nv = m.nv;
+  const T MJB_CONST* body_mass = prm_row<PRM_BODY_MASS>(c, m.body_mass, m.nbody);
   for (int i = lane; i < nq; i += G) w[L.qpos + i] = (T)d.qpos[(size_t)env * nq + i];
   gsync<G>();
   kinematics<T, G>(c);
@@ -309,13 +322,13 @@ __global__ __launch_bounds__(64) void k_jac(const DevModel<T>* mg, const Lay* lg
         for (int b = id > 0 ? id : 1; b < m.nbody; b++) {
           int p = b; bool inside = id == 0;
           while (p > 0 && !inside) { if (p == id) inside = true; p = m.body_parentid[p]; }
-          T mass = m.body_mass[b];
+          T mass = body_mass[b];
           if (!inside || mass <= 0) continue;
           T pt[3] = {w[L.xipos + 3 * b], w[L.xipos + 3 * b + 1], w[L.xipos + 3 * b + 2]}, tp[3];
           jac_col<T>(c, b, i, pt, tp, (T*)0);
           jp[0] += mass * tp[0]; jp[1] += mass * tp[1]; jp[2] += mass * tp[2];
         }
-        T sm = m.body_subtreemass[id];
+        T sm = prm_row<PRM_SUBTREEMASS>(c, m.body_subtreemass, m.nbody)[id];
         if (sm > Num<T>::minval()) { jp[0] /= sm; jp[1] /= sm; jp[2] /= sm; }
       } else {
         int b = kind == 0 ? m.site_bodyid[id] : id;

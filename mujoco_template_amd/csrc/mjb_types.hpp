@@ -101,6 +101,17 @@ struct Lay {
 
 constexpr int CON_STRIDE = 11;  // dist, pos[3], normal[3], tangent1[3], mu (friction[0]); tangent2 = n x t1; pair id in i_con_pair
 
+// Per-environment model parameters (mjb_set_env_param): slot k holds the [batch, n_k] rows of field k in both precisions, or null
+// where every environment reads the shared model table.  The first PRM_NFIELD slots are the fields a caller sets (the order of
+// MJB_PRM_* in mjbatch.h, and of the bits of MJB_SPEC_PARAMS); the two slots behind them are derived from those fields on the device
+// and are set exactly when their source is: body_subtreemass [nbody] (from body_mass), pair_friction [npair, 5] (from geom_friction).
+enum { PRM_BODY_MASS = 0, PRM_BODY_INERTIA, PRM_DOF_DAMPING, PRM_DOF_ARMATURE, PRM_ACT_GEAR, PRM_ACT_GAINPRM, PRM_ACT_BIASPRM,
+       PRM_GEOM_FRICTION, PRM_GRAVITY, PRM_NFIELD, PRM_SUBTREEMASS = PRM_NFIELD, PRM_PAIR_FRICTION, PRM_NSLOT };
+struct PrmRows {
+  const float MJB_CONST* f[PRM_NSLOT];    // fp32 copies ((float)double, as fill_dev_model rounds): read by the fp32 kernels
+  const double MJB_CONST* d[PRM_NSLOT];   // float64 masters: read by the float64 kernels (the FD kernel of fp32 data included)
+};
+
 // Device state of the batch (TS = storage type of the [batch, dof] arrays in HBM).
 template <typename TS>
 struct DevData {
@@ -116,6 +127,7 @@ struct DevData {
   unsigned long long* prof;   // per-phase cycle sums (diagnostic -DMJB_PROFILE build only; null otherwise)
   unsigned* sched;            // ticket mode of k_step: [0] next ticket
   unsigned long long* xfer;   // ticket mode: tagged hand-over buffer [batch, nq + 3 nv + 2] (env_run)
+  PrmRows prm;                // per-environment model parameters (all null: every environment reads the model)
 };
 enum { PH_KIN = 0, PH_COM, PH_CRB, PH_COLL, PH_CONS, PH_VEL, PH_ACT, PH_SOLVE, PH_INTEG, PH_OTHER, PH_SOL_DIR, PH_SOL_LS, PH_CNT_LS = 12, PH_CNT_DIR, PH_CNT_FACT, PH_SOL_MV, PH_FAC_LOAD = 16, PH_FAC_PANEL, PH_FAC_BACK, PH_FAC_ALL, PH_N = 24 };
 

@@ -117,6 +117,16 @@ class ShardPlan:
     def equal_shards(self) -> bool:
         return len(set(self.counts)) == 1
 
+    def local_rows(self, value, per_env_shape: tuple):
+        """This rank's block ``[count, *per_env_shape]`` of a ``[global_batch, *per_env_shape]`` array (numpy or torch, sliced without a
+        copy); a ``[*per_env_shape]`` value (the same for every environment) is returned as it is."""
+        shape = tuple(value.shape)
+        if shape == tuple(per_env_shape):
+            return value
+        if shape != (self.global_batch, *per_env_shape):
+            raise ValueError(f"expected shape {[self.global_batch, *per_env_shape]} (global batch) or {list(per_env_shape)}, got {list(shape)}")
+        return value[self.env0:self.env0 + self.count]
+
     def gather(self, local_obs, comm: "RcclCommunicator | None" = None, stream=None):
         """``[..., count, dim]`` of this rank -> ``[..., global_batch, dim]`` on every rank (rank order = environment order).  With an
         ``RcclCommunicator`` and equal shards the collective is the library's own C-ABI entry point ``mjb_allgather_obs``

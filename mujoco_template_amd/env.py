@@ -33,7 +33,7 @@ from typing import Any
 
 import numpy as np
 
-from ._capi import CTRL_FEEDBACK, CTRL_KEEP, CTRL_RANDOM, CTRL_ZERO
+from ._capi import CTRL_FEEDBACK, CTRL_KEEP, CTRL_RANDOM, CTRL_ZERO, env_param_shape
 from ._typing import InfoDict, JacobiansDict, Observation
 from .compat import check_controller_compat
 from .control import Controller, device_ctrl_mode_of, uses_device_arrays
@@ -197,6 +197,24 @@ class Env:
             # several example controllers write qpos/qvel/ctrl here
             self.controller.prepare(self.model, self.device_data if self._device_arrays else self.data)
         return self._ensure_extractor()(self.data)
+
+    # -- per-environment model parameters (domain randomisation) ------------------------------------
+    def set_model_params(self, envs=None, **fields) -> None:
+        """Per-environment values of model fields (``BatchSim.set_env_params``: ``body_mass``, ``body_inertia``, ``dof_damping``,
+        ``dof_armature``, ``actuator_gear``, ``actuator_gainprm``, ``actuator_biasprm``, ``geom_friction``, ``gravity``), each
+        ``[batch, *shape]`` or ``[*shape]``; torch tensors on the GPU stay there.  A sharded environment takes ``[GLOBAL batch, *shape]``
+        and keeps its ``ShardPlan`` block; ``envs`` selects among this process' environments as in ``reset(envs=)`` (e.g. the device
+        mask ``StepResult.done`` of a ``reset_done`` step, to re-sample the parameters of the environments that were just reset).  The
+        values hold until changed: resets leave them alone."""
+        sim = self.data.sim
+        if self.shard is not None:
+            fields = {k: self.shard.local_rows(v, env_param_shape(sim.model.compiled, k)) for k, v in fields.items()}
+        sim.use_torch_stream()
+        sim.set_env_params(envs, **fields)
+
+    def model_params(self, name: str) -> np.ndarray:
+        """``[batch, *shape]`` float64 values of a per-environment field of this process' environments (the model's where not set)."""
+        return self.data.sim.env_params(name)
 
     def _reset_envs(self, envs, keyframe, noise, seed, *, out=None):
         sim = self.data.sim
