@@ -279,7 +279,7 @@ static const std::map<std::string, Rule>& schema() {
   static const std::map<std::string, Rule> s = {
       {"mujoco", {{"model"}, {}, false}},
       {"compiler", {{"angle", "autolimits"}, {"meshdir", "texturedir", "assetdir", "strippath", "discardvisual", "balanceinertia", "boundmass", "boundinertia", "fusestatic", "usethread", "alignfree"}, false}},
-      {"option", {{"timestep", "gravity", "integrator", "density", "viscosity", "impratio", "tolerance", "iterations", "cone", "solver", "jacobian"},
+      {"option", {{"timestep", "gravity", "integrator", "density", "viscosity", "tolerance", "iterations", "cone", "solver", "jacobian"},
                   {"ls_iterations", "ls_tolerance", "noslip_tolerance", "ccd_tolerance", "mpr_tolerance", "apirate"}, false}},
       {"body", {uni({"name", "pos", "childclass"}, ORIENT), {"user"}, false}},
       {"joint", {{"name", "class", "type", "pos", "axis", "range", "limited", "damping", "stiffness", "armature", "margin", "ref", "springref", "solreflimit", "solimplimit"}, {"group", "user"}, false}},
@@ -313,7 +313,7 @@ static const std::map<std::string, std::map<std::string, std::string>>& rejects(
       {"body", {{"mocap", "mocap bodies"}, {"gravcomp", "gravity compensation"}}},
       {"fixed", {{"frictionloss", "tendon frictionloss"}, {"stiffness", "tendon springs"}, {"damping", "tendon damping"}, {"springlength", "tendon springs"}}},
       {"option", {{"wind", "wind"}, {"magnetic", ""}, {"o_margin", "contact overrides"}, {"o_solref", "contact overrides"}, {"o_solimp", "contact overrides"},
-                  {"o_friction", "contact overrides"}, {"noslip_iterations", "the noslip solver"}, {"actuatorgroupdisable", "actuatorgroupdisable (use opt.disableactuator)"}}},
+                  {"o_friction", "contact overrides"}, {"noslip_iterations", "the noslip solver"}, {"impratio", "impratio (frictional impedance ratio)"}, {"actuatorgroupdisable", "actuatorgroupdisable (use opt.disableactuator)"}}},
       {"compiler", {{"coordinate", ""}, {"eulerseq", ""}, {"settotalmass", "settotalmass"}, {"inertiafromgeom", ""}, {"inertiagrouprange", "inertiagrouprange"}}},
   };
   return r;
@@ -324,7 +324,7 @@ static const std::map<std::pair<std::string, std::string>, SS>& reject_ok() {
       {{"compiler", "coordinate"}, {"local"}}, {{"compiler", "eulerseq"}, {"xyz"}}, {{"compiler", "inertiafromgeom"}, {"true", "auto"}},
       {{"compiler", "settotalmass"}, {"-1"}}, {{"joint", "frictionloss"}, {"0"}}, {{"fixed", "frictionloss"}, {"0"}}, {{"fixed", "stiffness"}, {"0"}},
       {{"fixed", "damping"}, {"0"}}, {{"body", "mocap"}, {"false"}}, {{"body", "gravcomp"}, {"0"}}, {{"option", "wind"}, {"0 0 0"}},
-      {{"option", "noslip_iterations"}, {"0"}}, {{"option", "magnetic"}, {"*"}}};
+      {{"option", "noslip_iterations"}, {"0"}}, {{"option", "impratio"}, {"1"}}, {{"option", "magnetic"}, {"*"}}};
   return r;
 }
 static std::string squeeze(const std::string& s) {             // " ".join(s.split())
@@ -507,7 +507,7 @@ struct Compiler {
   bool autolimits = true;
   std::string model_name;
   // options
-  double timestep = 0.002, gravity[3] = {0, 0, -9.81}, density = 0, viscosity = 0, impratio = 1, tolerance = 1e-8, meaninertia = 1;
+  double timestep = 0.002, gravity[3] = {0, 0, -9.81}, density = 0, viscosity = 0, impratio = 1 /* only 1 is accepted */, tolerance = 1e-8, meaninertia = 1;
   int integrator = INT_EULER, iterations = 100, ls_iterations = 50, disableactuator = 0;
   std::vector<Body> bodies;
   std::vector<Joint> joints;
@@ -1164,7 +1164,6 @@ struct Compiler {
         }
         if (nonempty("density")) density = to_double(*e.get("density"));
         if (nonempty("viscosity")) viscosity = to_double(*e.get("viscosity"));
-        if (nonempty("impratio")) impratio = to_double(*e.get("impratio"));
         if (nonempty("tolerance")) tolerance = to_double(*e.get("tolerance"));
         if (nonempty("iterations")) iterations = to_int(*e.get("iterations"));
         for (const char* k : {"cone", "solver", "jacobian"})

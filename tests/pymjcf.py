@@ -79,7 +79,7 @@ _SCHEMA_ATTRS: dict[str, tuple[set[str], set[str]]] = {
     "mujoco": ({"model"}, set()),
     "compiler": ({"angle", "autolimits"}, {"meshdir", "texturedir", "assetdir", "strippath", "discardvisual", "balanceinertia", "boundmass",
                                             "boundinertia", "fusestatic", "usethread", "alignfree"}),
-    "option": ({"timestep", "gravity", "integrator", "density", "viscosity", "impratio", "tolerance", "iterations", "cone", "solver",
+    "option": ({"timestep", "gravity", "integrator", "density", "viscosity", "tolerance", "iterations", "cone", "solver",
                 "jacobian"}, {"ls_iterations", "ls_tolerance", "noslip_tolerance", "ccd_tolerance", "mpr_tolerance", "apirate"}),
     "body": ({"name", "pos", "childclass"} | _ORIENT, {"user"}),
     "joint": ({"name", "class", "type", "pos", "axis", "range", "limited", "damping", "stiffness", "armature", "margin", "ref", "springref",
@@ -111,14 +111,16 @@ _REJECT_ATTRS = {
     "body": {"mocap": "mocap bodies", "gravcomp": "gravity compensation"},
     "fixed": {"frictionloss": "tendon frictionloss", "stiffness": "tendon springs", "damping": "tendon damping", "springlength": "tendon springs"},
     "option": {"wind": "wind", "magnetic": None, "o_margin": "contact overrides", "o_solref": "contact overrides", "o_solimp": "contact overrides",
-               "o_friction": "contact overrides", "noslip_iterations": "the noslip solver", "actuatorgroupdisable": "actuatorgroupdisable (use opt.disableactuator)"},
+               "o_friction": "contact overrides", "noslip_iterations": "the noslip solver",
+               "impratio": "impratio (frictional impedance ratio)", "actuatorgroupdisable": "actuatorgroupdisable (use opt.disableactuator)"},
     "compiler": {"coordinate": None, "eulerseq": None, "settotalmass": "settotalmass", "inertiafromgeom": None, "inertiagrouprange": "inertiagrouprange"},
 }
 # rejected attributes that are harmless at these values (MuJoCo's defaults, or what the shipped models state explicitly)
 _REJECT_OK_VALUES = {("compiler", "coordinate"): {"local"}, ("compiler", "eulerseq"): {"xyz"}, ("compiler", "inertiafromgeom"): {"true", "auto"},
                      ("compiler", "settotalmass"): {"-1"}, ("joint", "frictionloss"): {"0"}, ("fixed", "frictionloss"): {"0"},
                      ("fixed", "stiffness"): {"0"}, ("fixed", "damping"): {"0"}, ("body", "mocap"): {"false"}, ("body", "gravcomp"): {"0"},
-                     ("option", "wind"): {"0 0 0"}, ("option", "noslip_iterations"): {"0"}, ("option", "magnetic"): None}     # None: any value
+                     ("option", "wind"): {"0 0 0"}, ("option", "noslip_iterations"): {"0"}, ("option", "impratio"): {"1"},
+                     ("option", "magnetic"): None}     # None: any value
 
 
 def _check_attrs(tag: str, elem: ET.Element, where: str) -> None:
@@ -324,8 +326,6 @@ class _Compiler:
                 m.density = float(opt.get("density"))
             if opt.get("viscosity"):
                 m.viscosity = float(opt.get("viscosity"))
-            if opt.get("impratio"):
-                m.impratio = float(opt.get("impratio"))
             if opt.get("tolerance"):
                 m.tolerance = float(opt.get("tolerance"))
             if opt.get("iterations"):

@@ -259,6 +259,7 @@ _REJECTS = {
     "noslip": ('<option noslip_iterations="3"/>', "noslip"),
     "override": ('<option o_margin="0.01"/>', "override"),
     "wind": ('<option wind="1 0 0"/>', "wind"),
+    "impratio": ('<option impratio="10"/>', "impratio"),
     "eulerseq": ('<compiler eulerseq="zyx"/>', "eulerseq"),
     "settotalmass": ('<compiler settotalmass="5"/>', "settotalmass"),
     "global coordinates": ('<compiler coordinate="global"/>', "coordinate"),
