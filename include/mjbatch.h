@@ -257,7 +257,10 @@ int mjb_set_feedback(mjbData* d, const double* K, const double* u0, const double
 int mjb_set_feedback_noise(mjbData* d, const double* noise_std, const double* noise_table, int nsteps, int env_stride);
 int mjb_feedback_ctrl(mjbData* d, int step);
 
-/* ---- observations: ObservationExtractor.__call__ with as_dict=False (reference observations.py:98-174) ---- */
+/* ---- observations: ObservationExtractor.__call__ with as_dict=False (reference observations.py:98-174) ----
+ * flags: bit 0 qpos, 1 qvel, 2 ctrl, 3 sensordata, 4 time, 6 body positions at the inertial frames, 7 (value 128) qacc_warmstart [nv],
+ * the solver's warm start after the step - no reference key; it comes LAST in the row, behind the sorted keys, so rows of specs
+ * without it are unchanged (the rollout ring of mjb_rollout_ctrl feeds it to mjb_transition_fd_points). */
 int mjb_obs_spec_create(mjbData* d, int flags, int nsite, const int* site_ids, int nbody, const int* body_ids,
                         int ngeom, const int* geom_ids, int nsubtree, const int* subtree_ids, mjbObsSpec** out);
 void mjb_obs_spec_free(mjbObsSpec* s);
@@ -277,6 +280,34 @@ int mjb_transition_fd(mjbData* d, double eps, int centered, double* A_host, doub
 /* the same without the final host copy: pointers to the library's PINNED result blocks (same layouts), valid until the next
  * mjb_transition_fd* call on this data object — at humanoid batch 512 the two blocks are 16.5 MB */
 int mjb_transition_fd_pinned(mjbData* d, double eps, int centered, const double** A_pinned, const double** B_pinned);
+
+/* ---- mjd_transitionFD at caller-chosen points: T x batch (state, control) points held in device memory, linearised in one submission
+ * with the results left on the device.  Replaces the reference's linearisation called once per step from a controller loop
+ * (mujoco_template/linearization.py:16-35 from runtime.py:631-663) when a whole trajectory is linearised (iLQR, time-varying LQR).
+ * Point (t, e), t in [0, T), e in [0, batch), reads x[t * x_step_stride + e * x_env_stride + i] of qpos [nq], qvel [nv], ctrl [nu] and
+ * qacc_warmstart [nv] (NULL = zeros at every point): device memory of the data's device in the data's dtype, strides in elements,
+ * >= 0 (0 = broadcast), so columns of a rollout ring [T, batch, dim] and a [batch, T, nu] control tensor are read in place.
+ * A_dev [T, batch, 2nv, 2nv], B_dev [T, batch, 2nv, nu]: float64 device memory of the caller, row-major, layout and signs of
+ * mjb_transition_fd.  Block (t, e) is bit for bit what mjb_transition_fd returns for environment e once the data's qpos, qvel, ctrl and
+ * qacc_warmstart rows of e hold point (t, e): e's per-environment parameter rows, the data's current options, the one-sided difference
+ * at a ctrlrange bound, every column restarting from the same warm start, the specialised kernel when one is loaded.
+ * The data's own state, time and engine flags are not touched.  Everything is enqueued on the data's stream; the call does not
+ * synchronise - except when the per-column scratch has to grow (the first call, or more points per slab than any call before): the old
+ * block is freed, which waits for the device.  The scratch is one block per data object: after mjb_set_stream to another stream, the
+ * next mjb_transition_fd* call makes that stream wait (an event, on the device) for the FD launches still queued on the old one.
+ * The points run in slabs whose per-column scratch stays under a fixed budget (MJB_FD_SLAB_BYTES overrides it), slab after
+ * slab on the stream; the result does not depend on the slab size.
+ * Checked before anything is launched (MJB_ERR_ARG, state and engine flags untouched): T >= 1, T * batch < 2^31, eps > 0, strides >= 0,
+ * every array of non-zero width non-NULL (qacc_warmstart excepted), device-accessible memory of the data's device
+ * (hipPointerGetAttributes), and the highest element read or written, (T-1)*step_stride + (batch-1)*env_stride + n-1, inside the
+ * allocation behind its pointer (hipMemGetAddressRange). */
+int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step_stride, long qpos_env_stride,
+                             const void* qvel, long qvel_step_stride, long qvel_env_stride,
+                             const void* ctrl, long ctrl_step_stride, long ctrl_env_stride,
+                             const void* qacc_warmstart, long ws_step_stride, long ws_env_stride,
+                             double eps, int centered, double* A_dev, double* B_dev);
+/* slabs the last mjb_transition_fd_points on this data object ran in (0: none yet) */
+int mjb_fd_points_slabs(const mjbData* d);
 
 /* ---- mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacSubtreeCom (reference jacobians.py:44-79).
  * kinds[i]: 0 site, 1 body, 2 bodycom, 3 subtreecom.  jacp/jacr host [batch, nreq, 3, nv] float64 (jacr may be NULL) ---- */

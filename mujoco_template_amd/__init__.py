@@ -22,7 +22,7 @@ from .jacobians import compute_requested_jacobians
 from .linearization import linearize_discrete
 from .model import ModelHandle
 from .observations import ObservationExtractor, ObservationProducer, ObservationSpec
-from .rollout import rollout
+from .rollout import linearize_rollout, rollout
 from .logging import DataProbe, StateControlRecorder
 from .runtime import StepHook, TrajectoryLogger, iterate_passive, run_passive_headless
 from .setpoints import steady_ctrl0
@@ -35,6 +35,6 @@ __all__ = [
     "ObservationProducer", "ModelHandle", "CompatibilityReport", "StepResult", "Env", "ZeroController",
     "PositionTargetDemo", "RandomCtrlController", "LinearFeedbackController", "check_controller_compat", "linearize_discrete",
     "compute_requested_jacobians", "StepHook", "iterate_passive", "run_passive_headless", "steady_ctrl0", "DataProbe",
-    "StateControlRecorder", "TrajectoryLogger", "rollout", "ObservationDict", "DeviceData", "uses_device_arrays",
+    "StateControlRecorder", "TrajectoryLogger", "rollout", "linearize_rollout", "ObservationDict", "DeviceData", "uses_device_arrays",
     "ObservationArray", "Observation", "JacobianDict", "JacobiansDict", "InfoDict", "StateSnapshot", "__version__",
 ]

@@ -102,6 +102,10 @@ def load_library() -> ctypes.CDLL:
     L.mjb_transition_fd.argtypes = [vp, cd, ci, vp, vp]
     L.mjb_transition_fd_pinned.argtypes = [vp, cd, ci, ctypes.POINTER(ctypes.POINTER(cd)), ctypes.POINTER(ctypes.POINTER(cd))]
     L.mjb_transition_fd_pinned.restype = ci
+    L.mjb_transition_fd_points.argtypes = [vp, ci, vp, cl, cl, vp, cl, cl, vp, cl, cl, vp, cl, cl, cd, ci, vp, vp]
+    L.mjb_transition_fd_points.restype = ci
+    L.mjb_fd_points_slabs.argtypes = [vp]
+    L.mjb_fd_points_slabs.restype = ci
     L.mjb_jac.argtypes = [vp, ci, vp, vp, vp, vp]
     L.mjb_profile_get.argtypes = [vp, vp]
     L.mjb_profile_get.restype = ci
@@ -887,6 +891,76 @@ class BatchSim:
         A = np.ctypeslib.as_array(pa, shape=(self.batch, 2 * m.nv, 2 * m.nv))
         Bv = np.ctypeslib.as_array(pb, shape=(self.batch, 2 * m.nv, m.nu)) if m.nu else np.zeros((self.batch, 2 * m.nv, 0))
         return (A.copy(), Bv.copy()) if copy else (A, Bv)
+
+    def transition_fd_points(self, qpos, qvel, ctrl, qacc_warmstart=None, *, eps: float = 1e-6, centered: bool = True, out=None):
+        """Finite-difference transition matrices at caller-chosen points (``mjb_transition_fd_points``): ``qpos [T, B, nq]``,
+        ``qvel [T, B, nv]``, ``ctrl [T, B, nu]`` and ``qacc_warmstart [T, B, nv]`` (``None`` = zeros) are torch tensors on this
+        object's GPU in the data's dtype, or ``[B, n]`` for one point per environment.  Their own strides address them: column views
+        of a rollout ring and ``expand``-ed tensors are read in place.  Returns ``(A [T, B, 2nv, 2nv], B [T, B, 2nv, nu])`` float64 on
+        the GPU (without the leading axis for ``[B, n]`` inputs), or fills ``out=(A, B)``.  Block ``(t, e)`` is bitwise what
+        ``transition_fd`` gives for environment ``e`` with the data's rows set to point ``(t, e)``; the data's own state is not
+        touched.  Enqueued on torch's current stream, nothing waits for the GPU; the inputs are kept referenced until the next call."""
+        import torch
+
+        m = self.model.compiled
+        nq, nv, nu, B = m.nq, m.nv, m.nu, self.batch
+        nx = 2 * nv
+        want = torch.float32 if self.dtype == "float32" else torch.float64
+        dev = torch.device(f"cuda:{self.device}")
+        lead = None
+        args, keep = [], []
+        for name, x, n, optional in (("qpos", qpos, nq, False), ("qvel", qvel, nv, False), ("ctrl", ctrl, nu, False),
+                                     ("qacc_warmstart", qacc_warmstart, nv, True)):
+            if x is None and optional:
+                args += [None, 0, 0]
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise ConfigError(f"transition_fd_points: {name} must be a torch tensor on {dev}, got {type(x).__name__}")
+            if x.dtype != want:
+                raise ConfigError(f"transition_fd_points: {name} must have the data's dtype {want}, got {x.dtype}")
+            if x.device != dev:
+                raise ConfigError(f"transition_fd_points: {name} must live on {dev}, got {x.device}")
+            if x.ndim not in (2, 3) or x.shape[-1] != n or x.shape[-2] != B:
+                raise ConfigError(f"transition_fd_points: {name} must have shape [T, {B}, {n}] or [{B}, {n}], got {list(x.shape)}")
+            T = 1 if x.ndim == 2 else int(x.shape[0])
+            if lead is None:
+                lead = (x.ndim, T)
+            elif lead != (x.ndim, T):
+                raise ConfigError(f"transition_fd_points: {name} has {list(x.shape)}: the inputs must agree in rank and in T")
+            if n > 1 and x.stride(-1) != 1:
+                x = x.contiguous()
+            ss, es = (0, x.stride(0)) if x.ndim == 2 else (x.stride(0), x.stride(1))
+            if ss < 0 or es < 0:
+                raise ConfigError(f"transition_fd_points: {name} has a negative stride")
+            keep.append(x)
+            args += [ctypes.c_void_p(x.data_ptr()) if x.numel() else None, int(ss), int(es)]
+        ndim, T = lead
+        if T < 1:
+            raise ConfigError("transition_fd_points: T must be >= 1")
+        if out is None:
+            A = torch.empty((T, B, nx, nx), device=dev, dtype=torch.float64)
+            Bm = torch.empty((T, B, nx, nu), device=dev, dtype=torch.float64)
+        else:
+            A, Bm = out
+            for name, x, shape in (("A", A, (T, B, nx, nx)), ("B", Bm, (T, B, nx, nu))):
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != dev or not x.is_contiguous() or \
+                        tuple(x.shape) not in (shape, shape[1:] if ndim == 2 else shape):
+                    raise ConfigError(f"transition_fd_points: out {name} must be a contiguous float64 tensor {list(shape)} on {dev}")
+        if not self._fd_spec_tried:                                # the per-model specialised kernel, by transition_fd's policy
+            self._fd_spec_tried = True
+            self._specialize_by_policy(self.specialize_fd, "finite-difference kernel", default=True)
+        self.use_torch_stream()
+        self._fd_points_keep = (keep, A, Bm)                        # alive at least until the next call on this object
+        _check(load_library().mjb_transition_fd_points(self.ptr, T, *args, float(eps), int(bool(centered)),
+                                                        ctypes.c_void_p(A.data_ptr()) if A.numel() else None,
+                                                        ctypes.c_void_p(Bm.data_ptr()) if Bm.numel() else None))
+        if out is not None:
+            return A, Bm
+        return (A[0], Bm[0]) if ndim == 2 else (A, Bm)
+
+    def fd_points_slabs(self) -> int:
+        """Slabs the last ``transition_fd_points`` ran in (``mjb_fd_points_slabs``)."""
+        return int(load_library().mjb_fd_points_slabs(self.ptr))
 
     def jac(self, kinds: Sequence[int], ids: Sequence[int]) -> tuple[np.ndarray, np.ndarray]:
         m = self.model.compiled

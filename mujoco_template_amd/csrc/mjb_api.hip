@@ -108,7 +108,11 @@ struct mjbData {
   unsigned long long ticket_next = 0;      // value of the device ticket counter when the next ticket launch starts
   int last_sched[6] = {0, 0, 0, 0, 0, 0};  // of the last mode-0 launch: steps, environment blocks, resident slots, chunk_steps, fair_bit, two waves per environment
   // fd / jac scratch
-  double *fd_y = nullptr, *fd_A = nullptr, *fd_B = nullptr;
+  double *fd_y = nullptr, *fd_A = nullptr, *fd_B = nullptr;  // fd_y / fd_valid: per-column scratch of fd_cap points (fd_scratch), grown on demand
+  size_t fd_cap = 0;
+  hipEvent_t fd_done = nullptr;                                // recorded behind the last FD launch: a call on ANOTHER stream waits for it before it reuses the scratch
+  hipStream_t fd_stream = nullptr; bool fd_pending = false;
+  int last_fd_slabs = 0;                                       // slabs of the last mjb_transition_fd_points (mjb_fd_points_slabs)
   double *fd_A_host = nullptr, *fd_B_host = nullptr;          // pinned: the (A, B) blocks leave the device in one async copy each
   // mjb_jac: persistent buffers (grown on demand) - the request (kinds | ids) in pinned memory the kernel reads directly, the result
   // blocks pinned (small requests: written by the kernel itself) and on the device (large requests: one async copy each)
@@ -760,6 +764,9 @@ void mjb_data_free(mjbData* d) {
   for (void* p : d->owned) (void)hipFree(p);
   if (d->mirror_host) (void)hipHostFree(d->mirror_host);
   std::free(d->mirror_shadow);
+  if (d->fd_y) (void)hipFree(d->fd_y);
+  if (d->fd_valid) (void)hipFree(d->fd_valid);
+  if (d->fd_done) (void)hipEventDestroy(d->fd_done);
   if (d->fd_A_host) (void)hipHostFree(d->fd_A_host);
   if (d->fd_B_host) (void)hipHostFree(d->fd_B_host);
   if (d->jac_req_pin) (void)hipHostFree(d->jac_req_pin);
@@ -1420,6 +1427,7 @@ int mjb_obs_spec_create(mjbData* d, int flags, int nsite, const int* site_ids, i
   if (flags & 4) dim += h.nu;
   if (flags & 8) dim += h.nsensordata;
   if (flags & 16) dim += 1;
+  if (flags & 128) dim += h.nv;
   s->dev.dim = dim;
   *out = s;
   return MJB_OK;
@@ -1445,63 +1453,176 @@ int mjb_obs_gather(mjbData* d, const mjbObsSpec* s, void* out_dev) {
   return MJB_OK;
 }
 
-static int transition_fd_impl(mjbData* d, double eps, int centered) {
-  if (!d) return fail(MJB_ERR_ARG, "NULL argument");
-  if (!(eps > 0)) return fail(MJB_ERR_ARG, "eps must be > 0");
+// Scratch budget of one slab of mjb_transition_fd_points (the per-column next states, fd_y): 66 KB per humanoid point, so ~2 000 points
+// per launch - several times what fills the chip.  MJB_FD_SLAB_BYTES overrides it (tests).
+static const unsigned long long kFdSlabBytes = 128ull << 20;
+
+// fd_y / fd_valid for `npoint` points: allocated once per data object and grown only when a larger slab comes
+static int fd_scratch(mjbData* d, size_t npoint, int ncol) {
+  if (npoint <= d->fd_cap) return MJB_OK;
   const HostModel& h = d->model->h;
-  HIPCHK(hipSetDevice(d->device));
-  { int rc0 = refresh_options(d); if (rc0 != MJB_OK) return rc0; }
-  const int nin = 2 * h.nv + h.nu, ncol = 1 + 2 * nin, nx = 2 * h.nv;
-  size_t B = (size_t)d->batch;
-  if (!d->fd_y) {
-    if (dev_alloc(d, &d->fd_y, B * ncol * (h.nq + h.nv)) || dev_alloc(d, &d->fd_valid, B * ncol) ||
-        dev_alloc(d, &d->fd_A, B * nx * nx) || dev_alloc(d, &d->fd_B, B * nx * (h.nu > 0 ? h.nu : 1)))
-      return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
-    HIPCHK(hipHostMalloc((void**)&d->fd_A_host, B * nx * nx * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&d->fd_B_host, B * nx * (h.nu > 0 ? h.nu : 1) * sizeof(double), hipHostMallocDefault));
+  if (d->fd_y) (void)hipFree(d->fd_y);                           // hipFree waits for the kernels that may still read it
+  if (d->fd_valid) (void)hipFree(d->fd_valid);
+  d->fd_y = nullptr; d->fd_valid = nullptr; d->fd_cap = 0;
+  if (hipMalloc((void**)&d->fd_y, npoint * ncol * (size_t)(h.nq + h.nv) * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&d->fd_valid, npoint * ncol * sizeof(int)) != hipSuccess) {
+    (void)hipGetLastError();
+    if (d->fd_y) (void)hipFree(d->fd_y);
+    d->fd_y = nullptr; d->fd_valid = nullptr;
+    return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
   }
-  // columns per job (k_fd shares the stages a chunk of columns cannot change): as many as keep >= ~4 jobs per residency slot,
-  // at most 8; a single environment keeps one column per job (latency over throughput)
-  int chunk = 8;
+  d->fd_cap = npoint;
+  return MJB_OK;
+}
+
+// The scratch is one block per data object and mjb_transition_fd_points does not synchronise: when the data's stream has changed
+// since the last FD launch (mjb_set_stream), the new stream first waits for that launch's event, so two calls never share the scratch.
+static int fd_order_begin(mjbData* d) {
+  if (d->fd_pending && d->fd_stream != d->stream) HIPCHK(hipStreamWaitEvent(d->stream, d->fd_done, 0));
+  return MJB_OK;
+}
+static int fd_order_end(mjbData* d) {
+  if (!d->fd_done) HIPCHK(hipEventCreateWithFlags(&d->fd_done, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(d->fd_done, d->stream));
+  d->fd_stream = d->stream; d->fd_pending = true;
+  return MJB_OK;
+}
+
+// One slab of points (pt.p0, pt.npoint set): the column kernel, then the combine kernel into the slab's (A, B) blocks; enqueued only.
+static int fd_run_slab(mjbData* d, const FdPoints& pt, double eps, int centered, double* A, double* B) {
+  const HostModel& h = d->model->h;
+  const int nin = 2 * h.nv + h.nu, ncol = 1 + 2 * nin;
+  { int rc = fd_scratch(d, (size_t)pt.npoint, ncol); if (rc != MJB_OK) return rc; }
+  // columns per job (k_fd shares the stages a chunk of columns cannot change), sized by the points of THIS launch
+  int chunk;
   {
     const size_t per_wg = (size_t)(64 / d->cfg.G_fd) * (size_t)d->cfg.Ld.bytes;
     size_t wg_per_cu = per_wg ? (size_t)160 * 1024 / per_wg : 8;
     if (wg_per_cu > 32) wg_per_cu = 32;
     if (wg_per_cu < 1) wg_per_cu = 1;
     const long slots = (long)wg_per_cu * d->ncu * (64 / d->cfg.G_fd);
-    const long want = (long)B * ncol / (4 * slots);
     if (const char* e = std::getenv("MJB_FD_CHUNK")) chunk = std::atoi(e);        // experiments (scripts/gpu_fd_timing.py)
-    else chunk = want < 1 ? 1 : (want > 8 ? 8 : (int)want);
+    else chunk = fd_chunk_rule(pt.npoint, ncol, slots);
+    if (chunk < 1) chunk = 1;
   }
   hipError_t e;
   if (d->spec[MJB_KERNEL_FD].fn) {                              // per-model specialised kernel: same arguments, same grid as launch_fd_g
-    if (chunk < 1) chunk = 1;
     const int epb = 64 / d->cfg.G_fd;
     const int njob = (1 + 2 * h.nu + chunk - 1) / chunk + (2 * h.nv + chunk - 1) / chunk + 2 * h.nv;
-    const long ngroups = (long)d->batch * njob;
+    const long ngroups = (long)pt.npoint * njob;
     const DevModel<double>* mg = d->md_dev; const Lay* lg = d->Ld_dev;
     DevData<float> dvf = d->df; DevData<double> dvd = d->dd;
-    int ncol_ = ncol, cv = chunk, cc = chunk; double eps_ = eps; double* yy = d->fd_y; int* vv = d->fd_valid;
-    void* args[] = {(void*)&mg, (void*)&lg, d->dtype == MJB_F32 ? (void*)&dvf : (void*)&dvd, (void*)&ncol_, (void*)&eps_, (void*)&yy, (void*)&vv, (void*)&cv, (void*)&cc};
+    int ncol_ = ncol, cv = chunk, cc = chunk; double eps_ = eps; double* yy = d->fd_y; int* vv = d->fd_valid; FdPoints pp = pt;
+    void* args[] = {(void*)&mg, (void*)&lg, d->dtype == MJB_F32 ? (void*)&dvf : (void*)&dvd, (void*)&ncol_, (void*)&eps_, (void*)&yy, (void*)&vv, (void*)&cv, (void*)&cc, (void*)&pp};
     e = hipModuleLaunchKernel(d->spec[MJB_KERNEL_FD].fn, (unsigned)((ngroups + epb - 1) / epb), 1, 1, 64, 1, 1, (unsigned)((size_t)epb * d->cfg.Ld.bytes), d->stream, args, nullptr);
   } else
-  e = d->dtype == MJB_F32 ? launch_fd<double, float>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->df, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream)
-                          : launch_fd<double, double>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream);
+  e = d->dtype == MJB_F32 ? launch_fd<double, float>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->df, pt, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream)
+                          : launch_fd<double, double>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, pt, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("fd launch: ") + hipGetErrorString(e));
-  long nthreads = (long)B * nin;
+  const long nthreads = (long)pt.npoint * nin;
+  hipLaunchKernelGGL(k_fd_combine<double>, dim3((unsigned)((nthreads + 127) / 128)), dim3(128), 0, d->stream, (const DevModel<double>*)d->md_dev, pt.npoint, ncol, centered, eps,
+                     (const double*)d->fd_y, (const int*)d->fd_valid, A, B);
+  HIPCHK(hipGetLastError());
+  return MJB_OK;
+}
+
+static int transition_fd_impl(mjbData* d, double eps, int centered) {
+  if (!d) return fail(MJB_ERR_ARG, "NULL argument");
+  if (!(eps > 0)) return fail(MJB_ERR_ARG, "eps must be > 0");
+  const HostModel& h = d->model->h;
+  HIPCHK(hipSetDevice(d->device));
+  { int rc0 = refresh_options(d); if (rc0 != MJB_OK) return rc0; }
+  const int nx = 2 * h.nv;
+  size_t B = (size_t)d->batch;
+  if (!d->fd_A) {
+    if (dev_alloc(d, &d->fd_A, B * nx * nx) || dev_alloc(d, &d->fd_B, B * nx * (h.nu > 0 ? h.nu : 1)))
+      return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
+    HIPCHK(hipHostMalloc((void**)&d->fd_A_host, B * nx * nx * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void**)&d->fd_B_host, B * nx * (h.nu > 0 ? h.nu : 1) * sizeof(double), hipHostMallocDefault));
+  }
+  // the point table of T = 1 over the data's own arrays: point e = environment e, one slab
+  FdPoints pt;
+  std::memset(&pt, 0, sizeof(pt));
+  if (d->dtype == MJB_F32) { pt.qpos = d->df.qpos; pt.qvel = d->df.qvel; pt.ctrl = d->df.ctrl; pt.warmstart = d->df.qacc_warmstart; }
+  else { pt.qpos = d->dd.qpos; pt.qvel = d->dd.qvel; pt.ctrl = d->dd.ctrl; pt.warmstart = d->dd.qacc_warmstart; }
+  pt.qpos_es = h.nq; pt.qvel_es = h.nv; pt.ctrl_es = h.nu; pt.ws_es = h.nv;
+  pt.p0 = 0; pt.npoint = d->batch;
   // a few environments (the reference's batch-1 loops with needs_linearization controllers): the combine kernel writes (A, B) straight
   // into the pinned result blocks (device-visible) - no staging copies; larger batches keep the device blocks + one async copy each
   const bool zero_copy = B * nx * (nx + (size_t)h.nu) * sizeof(double) <= (size_t)256 * 1024;
-  hipLaunchKernelGGL(k_fd_combine<double>, dim3((unsigned)((nthreads + 127) / 128)), dim3(128), 0, d->stream, (const DevModel<double>*)d->md_dev, d->batch, ncol, centered, eps,
-                     (const double*)d->fd_y, (const int*)d->fd_valid, zero_copy ? d->fd_A_host : d->fd_A, zero_copy ? d->fd_B_host : d->fd_B);
-  HIPCHK(hipGetLastError());
+  { int rc = fd_order_begin(d); if (rc != MJB_OK) return rc; }
+  { int rc = fd_run_slab(d, pt, eps, centered, zero_copy ? d->fd_A_host : d->fd_A, zero_copy ? d->fd_B_host : d->fd_B); if (rc != MJB_OK) return rc; }
   if (!zero_copy) {
     HIPCHK(hipMemcpyAsync(d->fd_A_host, d->fd_A, B * nx * nx * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     if (h.nu > 0) HIPCHK(hipMemcpyAsync(d->fd_B_host, d->fd_B, B * nx * h.nu * sizeof(double), hipMemcpyDeviceToHost, d->stream));
   }
   HIPCHK(hipStreamSynchronize(d->stream));
+  d->fd_pending = false;                                       // this stream has drained, and every earlier FD launch was ordered before it
   return MJB_OK;
 }
+
+// One strided [T, batch, n] input or output of mjb_transition_fd_points, checked as mjb_rollout_ctrl checks its control table
+static int check_fd_array(const mjbData* d, const char* what, const void* ptr, bool may_be_null, long T, long n, long ss, long es, size_t esize) {
+  const std::string pre = std::string("mjb_transition_fd_points: ") + what;
+  if (ss < 0 || es < 0) return fail(MJB_ERR_ARG, pre + ": strides must be >= 0");
+  if (n == 0) return MJB_OK;                                    // nothing is read: NULL allowed
+  if (!ptr) return may_be_null ? MJB_OK : fail(MJB_ERR_ARG, pre + " is NULL");
+  __int128 hi;
+  if (!fd_highest_element(T, d->batch, n, ss, es, hi)) return fail(MJB_ERR_ARG, pre + ": bad extent");
+  if (hi + 1 > ((__int128)1 << 60)) return fail(MJB_ERR_ARG, pre + ": the extent (T, batch, strides) lies beyond its allocation");
+  const int why = device_extent(d, ptr, (size_t)(hi + 1) * esize);
+  static const char* const msg[4] = {"", " is not device-accessible memory of this data object's device", ": no allocation found behind it",
+                                     ": the extent (T, batch, strides) lies beyond its allocation"};
+  return why ? fail(MJB_ERR_ARG, pre + msg[why]) : MJB_OK;
+}
+
+int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step_stride, long qpos_env_stride,
+                             const void* qvel, long qvel_step_stride, long qvel_env_stride,
+                             const void* ctrl, long ctrl_step_stride, long ctrl_env_stride,
+                             const void* qacc_warmstart, long ws_step_stride, long ws_env_stride,
+                             double eps, int centered, double* A_dev, double* B_dev) {
+  if (!d) return fail(MJB_ERR_ARG, "data is NULL");
+  if (T < 1) return fail(MJB_ERR_ARG, "mjb_transition_fd_points: T must be >= 1");
+  if (!(eps > 0)) return fail(MJB_ERR_ARG, "eps must be > 0");
+  const HostModel& h = d->model->h;
+  const long npoint = (long)T * d->batch;
+  if (npoint > 0x7fffffffL) return fail(MJB_ERR_ARG, "mjb_transition_fd_points: T * batch must fit 31 bits");
+  HIPCHK(hipSetDevice(d->device));
+  const size_t es = d->dtype == MJB_F32 ? 4 : 8;
+  const long nx = 2L * h.nv;
+  int rc;
+  if ((rc = check_fd_array(d, "qpos", qpos, false, T, h.nq, qpos_step_stride, qpos_env_stride, es)) != MJB_OK) return rc;
+  if ((rc = check_fd_array(d, "qvel", qvel, false, T, h.nv, qvel_step_stride, qvel_env_stride, es)) != MJB_OK) return rc;
+  if ((rc = check_fd_array(d, "ctrl", ctrl, false, T, h.nu, ctrl_step_stride, ctrl_env_stride, es)) != MJB_OK) return rc;
+  if ((rc = check_fd_array(d, "qacc_warmstart", qacc_warmstart, true, T, h.nv, ws_step_stride, ws_env_stride, es)) != MJB_OK) return rc;
+  if ((rc = check_fd_array(d, "A_dev", A_dev, false, T, nx * nx, (long)d->batch * nx * nx, nx * nx, 8)) != MJB_OK) return rc;
+  if ((rc = check_fd_array(d, "B_dev", B_dev, false, T, nx * h.nu, (long)d->batch * nx * h.nu, nx * h.nu, 8)) != MJB_OK) return rc;
+  if ((rc = refresh_options(d)) != MJB_OK) return rc;
+  FdPoints pt;
+  std::memset(&pt, 0, sizeof(pt));
+  pt.qpos = qpos; pt.qvel = qvel; pt.ctrl = ctrl; pt.warmstart = qacc_warmstart;
+  pt.qpos_ss = qpos_step_stride; pt.qpos_es = qpos_env_stride; pt.qvel_ss = qvel_step_stride; pt.qvel_es = qvel_env_stride;
+  pt.ctrl_ss = ctrl_step_stride; pt.ctrl_es = ctrl_env_stride; pt.ws_ss = ws_step_stride; pt.ws_es = ws_env_stride;
+  unsigned long long budget = kFdSlabBytes;
+  if (const char* e = std::getenv("MJB_FD_SLAB_BYTES")) { const long long v = std::atoll(e); if (v > 0) budget = (unsigned long long)v; }
+  const long per_slab = fd_slab_points(fd_point_scratch_bytes(h.nq, h.nv, h.nu), budget);
+  const long nslab = fd_slab_count(npoint, per_slab);
+  // the scratch of the largest slab, once, before anything is launched: growing it (the first call included) frees the old block, and
+  // hipFree waits for the device - the one case in which this call synchronises
+  if ((rc = fd_scratch(d, (size_t)(npoint < per_slab ? npoint : per_slab), 1 + 2 * (2 * h.nv + h.nu))) != MJB_OK) return rc;
+  if ((rc = fd_order_begin(d)) != MJB_OK) return rc;
+  for (long k = 0; k < nslab; k++) {                            // slab after slab on the stream: the scratch is reused in stream order
+    long p0 = 0, n = 0;
+    fd_slab(npoint, per_slab, k, p0, n);
+    pt.p0 = (int)p0; pt.npoint = (int)n;
+    rc = fd_run_slab(d, pt, eps, centered, A_dev + (size_t)p0 * nx * nx, B_dev ? B_dev + (size_t)p0 * nx * h.nu : nullptr);
+    if (rc != MJB_OK) return rc;
+  }
+  d->last_fd_slabs = (int)nslab;
+  return fd_order_end(d);
+}
+
+int mjb_fd_points_slabs(const mjbData* d) { return d ? d->last_fd_slabs : -1; }
 
 int mjb_transition_fd(mjbData* d, double eps, int centered, double* A_host, double* B_host) {
   if (!d || !A_host || !B_host) return fail(MJB_ERR_ARG, "NULL argument");

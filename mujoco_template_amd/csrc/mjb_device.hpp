@@ -2758,7 +2758,7 @@ MJB_DEV void reset_env_state(const ResetSpec& r, unsigned genv, unsigned episode
 }
 
 // flat observation (keys in sorted order, reference observations.py:171-174):
-// bodies_pos, ctrl, geoms_pos, qpos, qvel, sensordata, sites_pos, subtree_com, time
+// bodies_pos, ctrl, geoms_pos, qpos, qvel, sensordata, sites_pos, subtree_com, time; then (flag 128, the rollout ring) qacc_warmstart
 template <typename T, typename TS, int G> MJB_DEV void write_obs(const Ctx<T>& c, ObsRef s, double time, TS* out) {
   ModelRef<T> m = MJB_MODEL_OF(c.mp); LayRef L = *c.lp; const T* w = c.w; const int lane = c.lane;
   int o = 0;
@@ -2776,6 +2776,7 @@ template <typename T, typename TS, int G> MJB_DEV void write_obs(const Ctx<T>& c
   for (int i = lane; i < 3 * s.nsubtree; i += G) out[o + i] = (TS)w[L.subtree_com + 3 * s.subtree_ids[i / 3] + i % 3];
   o += 3 * s.nsubtree;
   if (s.flags & 16) { if (lane == 0) out[o] = (TS)time; o += 1; }
+  if (s.flags & 128) { for (int i = lane; i < m.nv; i += G) out[o + i] = (TS)w[L.qacc_ws + i]; o += m.nv; }   // what the launch would store had it ended here
 }
 
 // ---------------------------------------------------------------------------

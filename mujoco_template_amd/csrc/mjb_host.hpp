@@ -414,4 +414,48 @@ inline Lay make_layout(const HostModel& h, int ncon_max, int nefc_max, size_t si
   return L;
 }
 
+// ---------------------------------------------------------------------------
+// mjb_transition_fd_points: the host arithmetic of its argument checks and of its slab plan (no HIP: tested without a GPU)
+// ---------------------------------------------------------------------------
+// Highest element index a strided [T, B, n] array touches: (T-1) step_stride + (B-1) env_stride + n-1, in 128-bit arithmetic (no
+// overflow whatever the strides).  n == 0: nothing is touched, hi = -1.  false: T or B < 1, n < 0, or a negative stride.
+inline bool fd_highest_element(long T, long B, long n, long step_stride, long env_stride, __int128& hi) {
+  hi = -1;
+  if (T < 1 || B < 1 || n < 0 || step_stride < 0 || env_stride < 0) return false;
+  if (n == 0) return true;
+  hi = (__int128)(T - 1) * step_stride + (__int128)(B - 1) * env_stride + (n - 1);
+  return true;
+}
+// Do the elements [0, hi] of size esize behind ptr lie inside the allocation [base, base + size)?  (hi < 0: nothing to check)
+inline bool fd_extent_inside(unsigned long long ptr, __int128 hi, unsigned long long esize, unsigned long long base, unsigned long long size) {
+  if (hi < 0) return true;
+  const __int128 end = (__int128)ptr + (hi + 1) * (__int128)esize, limit = (__int128)base + (__int128)size;
+  return ptr >= base && end <= limit;
+}
+// Scratch of one point: the next states of its 1 + 2 (2 nv + nu) columns, float64
+inline unsigned long long fd_point_scratch_bytes(int nq, int nv, int nu) {
+  return (unsigned long long)(1 + 2 * (2 * nv + nu)) * (unsigned long long)(nq + nv) * 8ull;
+}
+// Points per slab under a scratch budget: as many as fit, at least one (a point larger than the budget still runs, alone)
+inline long fd_slab_points(unsigned long long bytes_per_point, unsigned long long budget) {
+  if (bytes_per_point == 0) bytes_per_point = 1;
+  const unsigned long long n = budget / bytes_per_point;
+  return n < 1 ? 1 : (n > 0x7fffffffull ? 0x7fffffffL : (long)n);
+}
+// Slab k of npoint points cut into slabs of per_slab: points [p0, p0 + n); false when k is past the last slab
+inline long fd_slab_count(long npoint, long per_slab) { return npoint < 1 || per_slab < 1 ? 0 : (npoint + per_slab - 1) / per_slab; }
+inline bool fd_slab(long npoint, long per_slab, long k, long& p0, long& n) {
+  if (k < 0 || k >= fd_slab_count(npoint, per_slab)) return false;
+  p0 = k * per_slab;
+  n = npoint - p0 < per_slab ? npoint - p0 : per_slab;
+  return true;
+}
+// Columns per job of k_fd for `npoint` points in one launch: as many as keep >= ~4 jobs per residency slot, at most 8; a single
+// point keeps one column per job (latency over throughput)
+inline int fd_chunk_rule(long npoint, int ncol, long slots) {
+  if (slots < 1) slots = 1;
+  const long want = npoint * ncol / (4 * slots);
+  return want < 1 ? 1 : (want > 8 ? 8 : (int)want);
+}
+
 }  // namespace mjb

@@ -144,8 +144,11 @@ namespace mjb {
 // Finite-difference columns of mjd_transitionFD (reference linearization.py:16-35): every column advances ONE perturbed replica
 // by one step and stores its next state.
 //   col 0 = nominal, col 1+2k = +eps on input k, col 2+2k = -eps;  k in [0, 2nv+nu): dq | dv | dctrl
-// y_out[(env*ncol + col) * (nq+nv)] = [qpos', qvel'];  valid[(env*ncol+col)] = 0 when a ctrl nudge left ctrlrange.
-// A lane-group runs one JOB = a chunk of columns of one kind of one environment, and - like MuJoCo's mj_stepSkip - computes the
+// The replicas start from the POINTS of a point table (FdPoints, mjb_types.hpp): point p = t * batch + e is the (qpos, qvel, ctrl, warm start)
+// row (t, e) of the caller's arrays and runs with environment e's parameter rows; a launch covers the slab [p0, p0 + npoint).
+// mjb_transition_fd is the table of T = 1 over the data's own arrays, mjb_transition_fd_points takes the arrays from the caller.
+// y_out[((p-p0)*ncol + col) * (nq+nv)] = [qpos', qvel'];  valid[(p-p0)*ncol+col] = 0 when a ctrl nudge left ctrlrange.
+// A lane-group runs one JOB = a chunk of columns of one kind of one point, and - like MuJoCo's mj_stepSkip - computes the
 // stages a column cannot change only ONCE per job, at the nominal state:
 //   ctrl jobs (the nominal column + 2 nu ctrl columns, `cc` per job): position + velocity stages shared, per column actuation -> solve -> Euler
 //   velocity jobs (2 nv columns, `cv` per job):                        position stage shared, per column constraint rows -> ... -> Euler
@@ -162,8 +165,25 @@ template <typename T, typename TS> MJB_DEV const PrmRows MJB_CONST* kernarg_prm(
   return &((const ModelDataKernArgs<T, TS> MJB_CONST*)__builtin_amdgcn_kernarg_segment_ptr())->d.prm;
 }
 
+// The argument list of k_fd / mjb_k_fd_spec as one struct (same member order, same natural alignment = the kernarg layout): the point
+// table is read through the kernarg segment, so that its base pointers and strides are scalar loads of the constant address space and
+// a point's row addresses are wave-uniform scalar arithmetic (one lane-group per wave; packed groups add one offset per group).
+template <typename T, typename TS> struct FdKernArgs { const DevModel<T>* mg; const Lay* lg; DevData<TS> d; int ncol; T eps; T* y_out; int* valid; int cv, cc; FdPoints pt; };
+// k_fd and mjb_k_fd_spec must keep exactly this parameter list (their last parameter `pt` is read through this struct, not by name):
+// the members the body relies on sit where the kernarg rules (natural alignment, declaration order) put the parameters
+typedef FdKernArgs<double, float> FkaDF;
+typedef FdKernArgs<double, double> FkaDD;
+static_assert(offsetof(FkaDF, mg) == 0 && offsetof(FkaDF, lg) == sizeof(void*) && offsetof(FkaDF, d) == offsetof(MdkaDD, d), "k_fd starts (mg, lg, d)");
+static_assert(offsetof(FkaDF, ncol) == offsetof(FkaDF, d) + sizeof(DevData<float>) && offsetof(FkaDF, eps) == offsetof(FkaDF, ncol) + 8 &&
+              offsetof(FkaDF, y_out) == offsetof(FkaDF, eps) + 8 && offsetof(FkaDF, valid) == offsetof(FkaDF, y_out) + 8 &&
+              offsetof(FkaDF, cv) == offsetof(FkaDF, valid) + 8 && offsetof(FkaDF, cc) == offsetof(FkaDF, cv) + 4 &&
+              offsetof(FkaDF, pt) == offsetof(FkaDF, cc) + 4, "(ncol, eps, y_out, valid, cv, cc, pt) follow d without padding beyond ncol's");
+static_assert(sizeof(DevData<float>) == sizeof(DevData<double>) && offsetof(FkaDD, pt) == offsetof(FkaDF, pt) && alignof(FdPoints) == 8 &&
+              sizeof(FkaDF) == offsetof(FkaDF, pt) + sizeof(FdPoints) && sizeof(FdPoints) == 12 * 8 + 2 * 4, "the point table is the last kernel argument");
+
 template <typename T, typename TS, int G>
 MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& d, int ncol, T eps, T* y_out, int* valid, int cv, int cc) {
+  const FdPoints MJB_CONST& pt = ((const FdKernArgs<T, TS> MJB_CONST*)__builtin_amdgcn_kernarg_segment_ptr())->pt;
   extern __shared__ __align__(16) char smem[];
   const int lane = threadIdx.x & (G - 1), sub = threadIdx.x / G;
   const long gid = (long)blockIdx.x * (64 / G) + sub;
@@ -173,8 +193,10 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
   MJB_SPEC_ASSUME(m) MJB_SPEC_ASSUME_LAY(L)
   const int nq = m.nq, nv = m.nv, nu = m.nu;
   const int nCj = (1 + 2 * nu + cc - 1) / cc, nVj = (2 * nv + cv - 1) / cv, nQj = 2 * nv, njob = nCj + nVj + nQj;
-  if (gid >= (long)d.batch * njob) return;
-  const int job = (int)(gid / d.batch), env = (int)(gid % d.batch);
+  if (gid >= (long)pt.npoint * njob) return;
+  const int job = (int)(gid / pt.npoint), pl = (int)(gid % pt.npoint);          // pl: the point's index in this slab
+  const int env = (pt.p0 + pl) % d.batch;
+  const long tp = (pt.p0 + pl) / d.batch;
   const bool rk4 = m.integrator == INT_RK4;
   int share, first, cnt, colbase;                               // share: 2 = position + velocity stages, 1 = position stage, 0 = nothing
   if (job < nCj) { share = 2; first = job * cc; cnt = 1 + 2 * nu - first; if (cnt > cc) cnt = cc; colbase = 4 * nv; }       // item i > 0 -> col 4 nv + i; item 0 -> col 0
@@ -187,14 +209,20 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
   for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;       // structural zeros of the mass matrix (crb_factor fills the rest)
   const int nstage = rk4 ? 4 : 1;
   for (int it = share > 0 ? -1 : 0; it < cnt; it++) {           // it = -1: the shared stages at the nominal state
-    for (int i = lane; i < nq; i += G) w[L.qpos + i] = (T)d.qpos[(size_t)env * nq + i];
-    for (int i = lane; i < nv; i += G) {
-      w[L.qvel + i] = (T)d.qvel[(size_t)env * nv + i];
-      w[L.qacc_ws + i] = (T)d.qacc_warmstart[(size_t)env * nv + i];
-      w[L.qacc + i] = 0;
-      w[L.Mv + i] = 0;
+    {                                                           // the point's rows: every column restarts from the same state and warm start
+      const TS* pq = (const TS*)pt.qpos + tp * pt.qpos_ss + (long)env * pt.qpos_es;
+      const TS* pv = (const TS*)pt.qvel + tp * pt.qvel_ss + (long)env * pt.qvel_es;
+      const TS* pc = (const TS*)pt.ctrl + tp * pt.ctrl_ss + (long)env * pt.ctrl_es;
+      const TS* pw = pt.warmstart ? (const TS*)pt.warmstart + tp * pt.ws_ss + (long)env * pt.ws_es : nullptr;
+      for (int i = lane; i < nq; i += G) w[L.qpos + i] = (T)pq[i];
+      for (int i = lane; i < nv; i += G) {
+        w[L.qvel + i] = (T)pv[i];
+        w[L.qacc_ws + i] = pw ? (T)pw[i] : (T)0;
+        w[L.qacc + i] = 0;
+        w[L.Mv + i] = 0;
+      }
+      for (int i = lane; i < nu; i += G) w[L.ctrl + i] = (T)pc[i];
     }
-    for (int i = lane; i < nu; i += G) w[L.ctrl + i] = (T)d.ctrl[(size_t)env * nu + i];
     gsync<G>();
     int ok = 1, col = 0;
     if (it >= 0) {
@@ -230,7 +258,7 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
     }
     if (!do_acc) continue;
     if (nstage == 1) euler<T, G>(c);
-    const size_t slot = (size_t)env * ncol + col;
+    const size_t slot = (size_t)pl * ncol + col;
     T* y = y_out + slot * (nq + nv);
     for (int i = lane; i < nq; i += G) y[i] = w[L.qpos + i];
     for (int i = lane; i < nv; i += G) y[nq + i] = w[L.qvel + i];
@@ -238,22 +266,23 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
     gsync<G>();
   }
 }
+// parameter list = FdKernArgs (static_asserts above): `pt` is read through the kernarg segment in k_fd_body
 template <typename T, typename TS, int G>
-__global__ __launch_bounds__(64) void k_fd(const DevModel<T>* mg, const Lay* lg, DevData<TS> d, int ncol, T eps, T* y_out, int* valid, int cv, int cc) {
+__global__ __launch_bounds__(64) void k_fd(const DevModel<T>* mg, const Lay* lg, DevData<TS> d, int ncol, T eps, T* y_out, int* valid, int cv, int cc, FdPoints pt) {
   k_fd_body<T, TS, G>(mg, lg, d, ncol, eps, y_out, valid, cv, cc);
 }
 #if defined(MJB_SPEC_KERNEL) && MJB_SPEC_KERNEL == 2
 }  // namespace mjb
 // The one kernel of a specialised FINITE-DIFFERENCE translation unit (mjb_fd_spec_source / mjb_fd_spec_load): k_fd<double, TS, G> with the
-// float64 layout's offsets and the model's sizes pinned and the model baked in as float64 constant data.
+// float64 layout's offsets and the model's sizes pinned and the model baked in as float64 constant data.  Parameter list = FdKernArgs.
 extern "C" __global__ __launch_bounds__(64) void mjb_k_fd_spec(const mjb::DevModel<double>* mg, const mjb::Lay* lg, mjb::DevData<MJB_SPEC_TS> d, int ncol, double eps,
-                                                               double* y_out, int* valid, int cv, int cc) {
+                                                               double* y_out, int* valid, int cv, int cc, mjb::FdPoints pt) {
   mjb::k_fd_body<double, MJB_SPEC_TS, MJB_SPEC_G>(mg, lg, d, ncol, eps, y_out, valid, cv, cc);
 }
 namespace mjb {
 #endif
 
-// A = d[dq';dv']/d[dq;dv]  (2nv x 2nv), B = d[dq';dv']/dctrl (2nv x nu), row-major per environment.
+// A = d[dq';dv']/d[dq;dv]  (2nv x 2nv), B = d[dq';dv']/dctrl (2nv x nu), row-major per point; `batch` = points of the slab, (A, B) its first blocks.
 template <typename T>
 __global__ void k_fd_combine(const DevModel<T>* mg, int batch, int ncol, int centered, T eps, const T* y, const int* valid, T* A, T* B) {
   ModelRef<T> m = *(const DevModel<T> MJB_CONST*)mg;
@@ -508,7 +537,8 @@ __global__ void k_obs(DevData<TS> d, int nq, int nv, int nu, int nbody, int ngeo
   off += 3 * s.nsite;
   for (int i = threadIdx.x; i < 3 * s.nsubtree; i += blockDim.x) o[off + i] = d.subtree_com[(size_t)env * 3 * nbody + 3 * s.subtree_ids[i / 3] + i % 3];
   off += 3 * s.nsubtree;
-  if (s.flags & 16) { if (threadIdx.x == 0) o[off] = (TS)d.time[env]; }
+  if (s.flags & 16) { if (threadIdx.x == 0) o[off] = (TS)d.time[env]; off += 1; }
+  if (s.flags & 128) { for (int i = threadIdx.x; i < nv; i += blockDim.x) o[off + i] = d.qacc_warmstart[(size_t)env * nv + i]; }
 }
 
 // ---------------------------------------------------------------------------
@@ -522,7 +552,7 @@ hipError_t launch_step2(const DevModel<T>* m, const Lay* Ldev, const Lay& L, con
 template <typename T, typename TS>
 int step_blocks_per_cu(int G, const Lay& L);       // resident workgroups of k_step per CU for this layout (<= 0: unknown)
 template <typename T, typename TS>
-hipError_t launch_fd(int G, const DevModel<T>* m, const Lay* Ldev, const Lay& L, const DevData<TS>& d, int ncol, int nv, int nu, int chunk, T eps, T* y, int* valid, hipStream_t stream);
+hipError_t launch_fd(int G, const DevModel<T>* m, const Lay* Ldev, const Lay& L, const DevData<TS>& d, const FdPoints& pt, int ncol, int nv, int nu, int chunk, T eps, T* y, int* valid, hipStream_t stream);
 template <typename T, typename TS>
 hipError_t launch_jac(int G, const DevModel<T>* m, const Lay* Ldev, const Lay& L, const DevData<TS>& d, int nreq, const int* kinds, const int* ids, T* out_p, T* out_r, hipStream_t stream);
 
@@ -567,7 +597,7 @@ int step_blocks_per_cu_g(const Lay& L) {
   return nb;
 }
 template <typename T, typename TS, int G>
-hipError_t launch_fd_g(const DevModel<T>* m, const Lay* Ldev, const Lay& L, const DevData<TS>& d, int ncol, int nv, int nu, int chunk, T eps, T* y, int* valid, hipStream_t stream) {
+hipError_t launch_fd_g(const DevModel<T>* m, const Lay* Ldev, const Lay& L, const DevData<TS>& d, const FdPoints& pt, int ncol, int nv, int nu, int chunk, T eps, T* y, int* valid, hipStream_t stream) {
   const int epb = 64 / G;
   size_t shmem = (size_t)epb * L.bytes;
   auto kern = k_fd<T, TS, G>;
@@ -575,9 +605,9 @@ hipError_t launch_fd_g(const DevModel<T>* m, const Lay* Ldev, const Lay& L, cons
   if (e != hipSuccess) return e;
   if (chunk < 1) chunk = 1;
   const int njob = (1 + 2 * nu + chunk - 1) / chunk + (2 * nv + chunk - 1) / chunk + 2 * nv;     // must match k_fd
-  long ngroups = (long)d.batch * njob;
+  long ngroups = (long)pt.npoint * njob;
   int grid = (int)((ngroups + epb - 1) / epb);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64), shmem, stream, m, Ldev, d, ncol, eps, y, valid, chunk, chunk);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64), shmem, stream, m, Ldev, d, ncol, eps, y, valid, chunk, chunk, pt);
   return hipGetLastError();
 }
 template <typename T, typename TS, int G>

@@ -141,9 +141,20 @@ struct DevDebug {
 };
 
 struct ObsSpecDev {
-  int flags;        // bit0 qpos, bit1 qvel, bit2 ctrl, bit3 sensordata, bit4 time, bit5 act(empty), bit6 bodies_inertial
+  int flags;        // bit0 qpos, bit1 qvel, bit2 ctrl, bit3 sensordata, bit4 time, bit5 act(empty), bit6 bodies_inertial,
+                    // bit7 qacc_warmstart [nv]: the solver's warm start after the step, LAST in the row (rows of specs without it are unchanged)
   int nsite, nbody, ngeom, nsubtree, dim;
   const int *site_ids, *body_ids, *geom_ids, *subtree_ids;
+};
+
+// Point table of the finite-difference kernel (k_fd): point p = t * batch + e, t in [0, T), reads row (t, e) of each array at
+// base + t * step stride + e * env stride (+ i), device memory in the storage dtype TS, strides in elements (>= 0, 0 = broadcast;
+// checked against the allocations on the host, fd_highest_element in mjb_host.hpp).  Environment e's parameter rows apply.
+// A launch covers the slab of points [p0, p0 + npoint); its scratch (y_out, valid) is indexed by p - p0.
+struct FdPoints {
+  const void *qpos, *qvel, *ctrl, *warmstart;   // warmstart null: zeros at every point
+  long qpos_ss, qpos_es, qvel_ss, qvel_es, ctrl_ss, ctrl_es, ws_ss, ws_es;
+  int p0, npoint;
 };
 
 struct StepArgs {

@@ -1,0 +1,112 @@
+"""iLQR on the cart-pole with ``linearize_rollout``: trajectory optimisation that never leaves the GPU between its three phases.
+
+Each iteration (horizon T, one nominal control sequence):
+  linearise  ``linearize_rollout`` - the nominal rollout and (A_t, B_t) at every step of it, two submissions;
+  backward   the Riccati recursion in torch float64 on the GPU -> feed-forward k_t and gains K_t;
+  forward    a line search over --alphas step sizes as ONE ``rollout`` (one environment per alpha).  The rollout is open loop, so
+             the candidate controls come from the closed loop run on the LINEARISED dynamics: dx' = A dx + B du,
+             du = alpha k + K dx; the true cost of each candidate is evaluated on the simulated states and the best one is kept.
+The pole starts tilted by --tilt rad; the cost asks for the upright pole at the origin.  Prints one JSON line: cost per iteration,
+the tilt at the end of the final trajectory and the wall time of each phase (each closed by a device synchronise).
+
+    python scripts/gpu_ilqr_cartpole.py [--horizon 100] [--iters 15] [--alphas 16] [--tilt 0.3] [--out FILE.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from mujoco_template_amd import linearize_rollout, mj, rollout  # noqa: E402
+
+XML = os.path.join(ROOT, "models", "cartpole.xml")
+U_MAX = 4.0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--horizon", type=int, default=100)
+    ap.add_argument("--iters", type=int, default=15)
+    ap.add_argument("--alphas", type=int, default=16)
+    ap.add_argument("--tilt", type=float, default=0.3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: the rollouts and linearisations run on the MI355X")
+    T, K = args.horizon, args.alphas
+    dev, f64 = torch.device("cuda"), torch.float64
+    model = mj.MjModel.from_xml_path(XML)
+    nq, nv, nu = model.nq, model.nv, model.nu
+    nx = 2 * nv
+    nominal = mj.MjData(model, batch=1, dtype="float64")
+    search = mj.MjData(model, batch=K, dtype="float64")
+    x0 = torch.zeros(1 + nq + nv, dtype=f64)
+    x0[2] = args.tilt                                                          # time, slider, hinge, slider vel, hinge vel
+    Q = torch.diag(torch.tensor([0.5, 10.0, 0.05, 0.1], dtype=f64, device=dev))
+    Qf = 20.0 * Q
+    R = 0.01 * torch.eye(nu, dtype=f64, device=dev)
+    alphas = torch.cat([torch.tensor([0.0]), torch.logspace(0, -3, K - 1)]).to(dev, f64)   # alpha 0: the nominal itself
+
+    def cost(state, u):
+        """[B] cost of states [B, T, 1+nq+nv] (after each step) under controls [B, T, nu]; the goal is the origin."""
+        x = state[..., 1:]
+        run = 0.5 * torch.einsum("bti,ij,btj->b", x[:, :-1], Q, x[:, :-1]) + 0.5 * torch.einsum("bti,ij,btj->b", u, R, u)
+        return run + 0.5 * torch.einsum("bi,ij,bj->b", x[:, -1], Qf, x[:, -1])
+
+    u = torch.zeros((1, T, nu), dtype=f64, device=dev)
+    costs, split = [], {"linearise": 0.0, "backward": 0.0, "forward": 0.0}
+    reg = 1e-6
+    for _ in range(args.iters):
+        t0 = time.perf_counter()
+        state, _, A, Bm = linearize_rollout(model, nominal, u, initial_state=x0)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        costs.append(float(cost(state, u)[0]))
+        xs = torch.cat([x0[1:].to(dev)[None], state[0, :, 1:]])                # [T + 1, nx]: x_t before step t, x_T the last state
+        A, Bm = A[0], Bm[0]
+        Vx, Vxx = Qf @ xs[T], Qf.clone()
+        ks, Ks = torch.zeros((T, nu), dtype=f64, device=dev), torch.zeros((T, nu, nx), dtype=f64, device=dev)
+        for t in range(T - 1, -1, -1):
+            lx = Q @ xs[t] if t > 0 else torch.zeros(nx, dtype=f64, device=dev)
+            Qx, Qu = lx + A[t].T @ Vx, R @ u[0, t] + Bm[t].T @ Vx
+            Qxx, Quu, Qux = (Q if t > 0 else 0 * Q) + A[t].T @ Vxx @ A[t], R + Bm[t].T @ Vxx @ Bm[t] + reg * torch.eye(nu, dtype=f64, device=dev), Bm[t].T @ Vxx @ A[t]
+            ks[t], Ks[t] = -torch.linalg.solve(Quu, Qu), -torch.linalg.solve(Quu, Qux)
+            Vx = Qx + Ks[t].T @ Quu @ ks[t] + Ks[t].T @ Qu + Qux.T @ ks[t]
+            Vxx = Qxx + Ks[t].T @ Quu @ Ks[t] + Ks[t].T @ Qux + Qux.T @ Ks[t]
+            Vxx = 0.5 * (Vxx + Vxx.T)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        dx = torch.zeros((K, nx), dtype=f64, device=dev)                       # closed loop on the linearised dynamics, all alphas at once
+        cand = torch.empty((K, T, nu), dtype=f64, device=dev)
+        for t in range(T):
+            du = alphas[:, None] * ks[t][None] + dx @ Ks[t].T
+            cand[:, t] = (u[0, t][None] + du).clamp(-U_MAX, U_MAX)
+            dx = dx @ A[t].T + (cand[:, t] - u[0, t][None]) @ Bm[t].T
+        st, _ = rollout(model, search, cand, initial_state=x0)
+        c = cost(st, cand)
+        best = int(torch.argmin(torch.nan_to_num(c, nan=float("inf"))))
+        u = cand[best:best + 1].clone()
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        split["linearise"] += t1 - t0; split["backward"] += t2 - t1; split["forward"] += t3 - t2
+    state, _ = rollout(model, nominal, u, initial_state=x0)
+    costs.append(float(cost(state, u)[0]))
+    res = {"horizon": T, "iterations": args.iters, "alphas": K, "tilt0_rad": args.tilt, "cost_per_iteration": costs,
+           "final_tilt_rad": float(state[0, -1, 2]), "final_slider_m": float(state[0, -1, 1]),
+           "wall_s": {k: v for k, v in split.items()}, "wall_share": {k: v / sum(split.values()) for k, v in split.items()}}
+    print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
