@@ -309,6 +309,56 @@ int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step
 /* slabs the last mjb_transition_fd_points on this data object ran in (0: none yet) */
 int mjb_fd_points_slabs(const mjbData* d);
 
+/* ---- batched LQR / iLQR on the arrays above: the backward (Riccati) recursion and the line search's candidate controls.  The
+ * reference designs its controllers from ONE (A, B) with scipy.linalg.solve_discrete_are (examples/humanoid/controllers/lqr.py:114);
+ * this is the finite-horizon, time-varying form of that recursion along a trajectory, fed by mjb_transition_fd_points.
+ * Everything is float64 DEVICE memory, row-major.  An mjbStrided array holds block (t, e) at ptr + t * step_stride + e * env_stride
+ * (strides in elements, >= 0, 0 = broadcast), so the [T, batch, ...] blocks of mjb_transition_fd_points, their permuted
+ * [batch, T, ...] views and a constant Q, R passed once (both strides 0) are read in place.  `batch` is the number of trajectories
+ * of THIS call - it need not be the data object's batch, which only supplies the device and the stream.
+ * Both calls check, before anything is launched (MJB_ERR_ARG with a message, outputs untouched): 1 <= nx <= 64, 1 <= nu <= 32, T >= 1,
+ * batch >= 1, strides >= 0, every required pointer non-NULL and device-accessible memory of the data's device
+ * (hipPointerGetAttributes), and the highest element read or written inside the allocation behind it (hipMemGetAddressRange).
+ * Both are enqueued on the data's stream as ONE kernel launch, use no scratch memory, copy nothing to the host and do not synchronise. */
+typedef struct mjbStrided { const double* ptr; long step_stride, env_stride; } mjbStrided;
+
+/* For every trajectory e and t = T-1 .. 0, from Vx = VxT, Vxx = VxxT (the Gauss-Newton form: no second-order dynamics terms):
+ *   Qx = lx + A' Vx, Qu = lu + B' Vx, Qxx = lxx + A' Vxx A, Quu = luu + B' Vxx B + mu I, Qux = lux + B' Vxx A,
+ *   k = -Quu^-1 Qu, K = -Quu^-1 Qux (Cholesky), dV[0] += k' Qu, dV[1] += k' Quu k / 2,
+ *   Vx = Qx + K' Quu k + K' Qu + Qux' k, Vxx = sym(Qxx + K' Quu K + K' Qux + Qux' K).
+ * With lx = lu = 0 this is the discrete Riccati recursion and K_t the time-varying LQR gain.
+ * A [nx, nx], B [nx, nu], lx [nx], lu [nu], lxx [nx, nx], luu [nu, nu], lux [nu, nx] (ptr NULL = 0) per (t, e); VxT [nx], VxxT [nx, nx]
+ * (symmetric), mu [1] per e (step_stride ignored).  Outputs, dense: k [T, batch, nu], K [T, batch, nu, nx], dV [batch, 2],
+ * status [batch] int32, and optionally (NULL = not wanted) V0x [batch, nx], V0xx [batch, nx, nx].
+ * status[e] = 0, or 1 + t for the first (highest) step t at which the Cholesky of Quu met a pivot that is <= 0 or not finite: that
+ * trajectory stops there, its k, K blocks of steps <= t, its dV, V0x, V0xx are written as zeros, the others are unaffected - an
+ * ordinary outcome of an iLQR iteration (the caller raises mu), reported through memory and not an error of the call. */
+typedef struct mjbLqrBackward {
+  int T, batch, nx, nu;
+  mjbStrided A, B, lx, lu, lxx, luu, lux;
+  mjbStrided VxT, VxxT, mu;
+  double *k, *K, *dV, *V0x, *V0xx;
+  int* status;
+} mjbLqrBackward;
+int mjb_lqr_backward(mjbData* d, const mjbLqrBackward* p);
+
+/* For every trajectory e and step size alphas[j], from dx = dx0[e] (ptr NULL = 0; step_stride ignored):
+ *   c_t = clamp(u_t + alphas[j] k_t + K_t dx, lo, hi),  dx = A_t dx + B_t (c_t - u_t)     for t = 0 .. T-1
+ * cand [batch, nalpha, T, nu] dense, float64 or (out_f32 != 0) float32 = the float64 value rounded once - what mjb_rollout_ctrl of a
+ * float32 data object takes.  k [nu], K [nu, nx], u [nu] per (t, e): the outputs of mjb_lqr_backward are passed with
+ * step_stride = batch * n, env_stride = n.  alphas [nalpha], 1 <= nalpha <= 64; lo / hi [nu], NULL = unbounded on that side. */
+typedef struct mjbLqrCandidates {
+  int T, batch, nx, nu, nalpha, out_f32;
+  mjbStrided A, B, k, K, u, dx0;
+  const double *alphas, *lo, *hi;
+  void* cand;
+} mjbLqrCandidates;
+int mjb_lqr_candidates(mjbData* d, const mjbLqrCandidates* p);
+
+/* c [M, N] = a' b for a [K, M], b [K, N] (device float64, dense, M, N <= 64, K >= 1) through the tile product of the two kernels
+ * above alone: a diagnostic that pins the operand and result fragment maps of v_mfma_f64_16x16x4_f64 with exact integer data. */
+int mjb_lqr_gemm_tn(mjbData* d, int M, int N, int K, const double* a, const double* b, double* c);
+
 /* ---- mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacSubtreeCom (reference jacobians.py:44-79).
  * kinds[i]: 0 site, 1 body, 2 bodycom, 3 subtreecom.  jacp/jacr host [batch, nreq, 3, nv] float64 (jacr may be NULL) ---- */
 int mjb_jac(mjbData* d, int nreq, const int* kinds, const int* ids, double* jacp_host, double* jacr_host);

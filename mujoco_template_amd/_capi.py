@@ -37,6 +37,25 @@ def build_library(force: bool = False) -> str:
     return _LIB_PATH
 
 
+class Strided(ctypes.Structure):
+    """``mjbStrided``: block (t, e) at ptr + t * step_stride + e * env_stride, strides in elements."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("step_stride", ctypes.c_long), ("env_stride", ctypes.c_long)]
+
+
+class LqrBackwardStruct(ctypes.Structure):
+    """``mjbLqrBackward`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("T", "batch", "nx", "nu")] + \
+               [(n, Strided) for n in ("A", "B", "lx", "lu", "lxx", "luu", "lux", "VxT", "VxxT", "mu")] + \
+               [(n, ctypes.c_void_p) for n in ("k", "K", "dV", "V0x", "V0xx", "status")]
+
+
+class LqrCandidatesStruct(ctypes.Structure):
+    """``mjbLqrCandidates`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("T", "batch", "nx", "nu", "nalpha", "out_f32")] + \
+               [(n, Strided) for n in ("A", "B", "k", "K", "u", "dx0")] + \
+               [(n, ctypes.c_void_p) for n in ("alphas", "lo", "hi", "cand")]
+
+
 def load_library() -> ctypes.CDLL:
     global _LIB
     if _LIB is not None:
@@ -106,6 +125,12 @@ def load_library() -> ctypes.CDLL:
     L.mjb_transition_fd_points.restype = ci
     L.mjb_fd_points_slabs.argtypes = [vp]
     L.mjb_fd_points_slabs.restype = ci
+    L.mjb_lqr_backward.argtypes = [vp, ctypes.POINTER(LqrBackwardStruct)]
+    L.mjb_lqr_backward.restype = ci
+    L.mjb_lqr_candidates.argtypes = [vp, ctypes.POINTER(LqrCandidatesStruct)]
+    L.mjb_lqr_candidates.restype = ci
+    L.mjb_lqr_gemm_tn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+    L.mjb_lqr_gemm_tn.restype = ci
     L.mjb_jac.argtypes = [vp, ci, vp, vp, vp, vp]
     L.mjb_profile_get.argtypes = [vp, vp]
     L.mjb_profile_get.restype = ci
@@ -961,6 +986,38 @@ class BatchSim:
     def fd_points_slabs(self) -> int:
         """Slabs the last ``transition_fd_points`` ran in (``mjb_fd_points_slabs``)."""
         return int(load_library().mjb_fd_points_slabs(self.ptr))
+
+    def _lqr_call(self, fn, struct, sizes: dict, arrays: dict, pointers: dict, keep) -> None:
+        for k, v in sizes.items():
+            setattr(struct, k, int(v))
+        for k, (ptr, ss, es) in arrays.items():
+            setattr(struct, k, Strided(ptr or None, int(ss), int(es)))
+        for k, ptr in pointers.items():
+            setattr(struct, k, ptr or None)
+        self.use_torch_stream()
+        self._lqr_keep = keep                                       # temporaries made for this call (possibly on another stream): alive until the next call
+        _check(fn(self.ptr, ctypes.byref(struct)))
+
+    def lqr_backward(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_lqr_backward`` on raw device addresses: ``sizes`` T, batch, nx, nu; ``arrays`` name -> (address, step stride,
+        env stride) of the ``mjbStrided`` inputs; ``pointers`` name -> address of the dense outputs; ``keep``: temporaries of the caller to hold until the next call (the outputs
+        need none: they are allocated on the stream the kernel runs on).  Enqueued on torch's current
+        stream, nothing waits for the GPU.  ``trajopt.lqr_backward`` is the checked tensor interface on top of it."""
+        self._lqr_call(load_library().mjb_lqr_backward, LqrBackwardStruct(), sizes, arrays, pointers, keep)
+
+    def lqr_candidates(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_lqr_candidates`` on raw device addresses (see ``lqr_backward``)."""
+        self._lqr_call(load_library().mjb_lqr_candidates, LqrCandidatesStruct(), sizes, arrays, pointers, keep)
+
+    def lqr_gemm_tn(self, a, b):
+        """``a [K, M]``, ``b [K, N]`` float64 tensors on this GPU -> ``a.T @ b`` through the kernels' f64 MFMA tile product alone."""
+        import torch
+
+        a, b = a.contiguous(), b.contiguous()
+        c = torch.empty((a.shape[1], b.shape[1]), dtype=torch.float64, device=a.device)
+        self.use_torch_stream()
+        _check(load_library().mjb_lqr_gemm_tn(self.ptr, int(a.shape[1]), int(b.shape[1]), int(a.shape[0]), a.data_ptr(), b.data_ptr(), c.data_ptr()))
+        return c
 
     def jac(self, kinds: Sequence[int], ids: Sequence[int]) -> tuple[np.ndarray, np.ndarray]:
         m = self.model.compiled

@@ -17,6 +17,7 @@
 #include "../../include/mjbatch.h"
 #include "mjb_host.hpp"
 #include "mjb_kernels.hpp"
+#include "mjb_lqr.hpp"
 
 using namespace mjb;
 
@@ -1623,6 +1624,100 @@ int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step
 }
 
 int mjb_fd_points_slabs(const mjbData* d) { return d ? d->last_fd_slabs : -1; }
+
+// ---- mjb_lqr_backward / mjb_lqr_candidates: the checks; the kernels and their launches are in mjb_lqr.hip ----
+// One strided float64 (or esize-byte) array of `n` elements per (t, e), T x B blocks: pointer, strides, extent
+static int check_lqr_array(const mjbData* d, const char* fn, const char* what, const void* ptr, bool may_be_null, long T, long B, long n,
+                           long ss, long es, size_t esize = 8) {
+  const std::string pre = std::string(fn) + ": " + what;
+  if (ss < 0 || es < 0) return fail(MJB_ERR_ARG, pre + ": strides must be >= 0");
+  if (!ptr) return may_be_null ? MJB_OK : fail(MJB_ERR_ARG, pre + " is NULL");
+  __int128 hi;
+  if (!lqr_highest_element(T, B, n, ss, es, hi)) return fail(MJB_ERR_ARG, pre + ": bad extent");
+  if (hi + 1 > ((__int128)1 << 60)) return fail(MJB_ERR_ARG, pre + ": the extent (T, batch, strides) lies beyond its allocation");
+  const int why = device_extent(d, ptr, (size_t)(hi + 1) * esize);
+  static const char* const msg[4] = {"", " is not device-accessible memory of this data object's device", ": no allocation found behind it",
+                                     ": the extent (T, batch, strides) lies beyond its allocation"};
+  return why ? fail(MJB_ERR_ARG, pre + msg[why]) : MJB_OK;
+}
+static int check_lqr_sizes(const char* fn, long T, long B, long nx, long nu) {
+  static const char* const msg[6] = {"", ": T must be >= 1", ": batch must be >= 1", ": nx must lie in [1, 64] (the state the kernel keeps in LDS)",
+                                     ": nu must lie in [1, 32]", ": T * batch * nu * nx is too large"};
+  const int why = lqr_size_error(T, B, nx, nu);
+  return why ? fail(MJB_ERR_ARG, std::string(fn) + msg[why]) : MJB_OK;
+}
+static LqrStrided lqr_arr(const mjbStrided& s) { LqrStrided r; r.p = s.ptr; r.ss = s.step_stride; r.es = s.env_stride; return r; }
+
+int mjb_lqr_backward(mjbData* d, const mjbLqrBackward* p) {
+  static const char* fn = "mjb_lqr_backward";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_lqr_backward: NULL argument");
+  int rc;
+  if ((rc = check_lqr_sizes(fn, p->T, p->batch, p->nx, p->nu)) != MJB_OK) return rc;
+  HIPCHK(hipSetDevice(d->device));
+  const long T = p->T, B = p->batch, nx = p->nx, nu = p->nu;
+  const struct { const char* what; const mjbStrided* s; long n; bool opt; } in[] = {
+      {"A", &p->A, nx * nx, false}, {"B", &p->B, nx * nu, false}, {"lx", &p->lx, nx, false}, {"lu", &p->lu, nu, false},
+      {"lxx", &p->lxx, nx * nx, false}, {"luu", &p->luu, nu * nu, false}, {"lux", &p->lux, nu * nx, true}};
+  for (const auto& a : in)
+    if ((rc = check_lqr_array(d, fn, a.what, a.s->ptr, a.opt, T, B, a.n, a.s->step_stride, a.s->env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "VxT", p->VxT.ptr, false, 1, B, nx, 0, p->VxT.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "VxxT", p->VxxT.ptr, false, 1, B, nx * nx, 0, p->VxxT.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "mu", p->mu.ptr, false, 1, B, 1, 0, p->mu.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "k", p->k, false, T, B, nu, B * nu, nu)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "K", p->K, false, T, B, nu * nx, B * nu * nx, nu * nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "dV", p->dV, false, 1, B, 2, 0, 2)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "V0x", p->V0x, true, 1, B, nx, 0, nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "V0xx", p->V0xx, true, 1, B, nx * nx, 0, nx * nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "status", p->status, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  LqrBackwardArgs a;
+  a.T = p->T; a.B = p->batch; a.nx = p->nx; a.nu = p->nu;
+  a.A = lqr_arr(p->A); a.Bm = lqr_arr(p->B); a.lx = lqr_arr(p->lx); a.lu = lqr_arr(p->lu); a.lxx = lqr_arr(p->lxx); a.luu = lqr_arr(p->luu);
+  a.lux = lqr_arr(p->lux); a.VxT = lqr_arr(p->VxT); a.VxxT = lqr_arr(p->VxxT); a.mu = lqr_arr(p->mu);
+  a.k = p->k; a.K = p->K; a.dV = p->dV; a.V0x = p->V0x; a.V0xx = p->V0xx; a.status = p->status;
+  const hipError_t e = lqr_launch_backward(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_backward launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+int mjb_lqr_candidates(mjbData* d, const mjbLqrCandidates* p) {
+  static const char* fn = "mjb_lqr_candidates";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_lqr_candidates: NULL argument");
+  int rc;
+  if ((rc = check_lqr_sizes(fn, p->T, p->batch, p->nx, p->nu)) != MJB_OK) return rc;
+  if (p->nalpha < 1 || p->nalpha > kLqrMaxAlpha) return fail(MJB_ERR_ARG, "mjb_lqr_candidates: nalpha must lie in [1, 64]");
+  HIPCHK(hipSetDevice(d->device));
+  const long T = p->T, B = p->batch, nx = p->nx, nu = p->nu, na = p->nalpha;
+  const struct { const char* what; const mjbStrided* s; long n; } in[] = {
+      {"A", &p->A, nx * nx}, {"B", &p->B, nx * nu}, {"k", &p->k, nu}, {"K", &p->K, nu * nx}, {"u", &p->u, nu}};
+  for (const auto& a : in)
+    if ((rc = check_lqr_array(d, fn, a.what, a.s->ptr, false, T, B, a.n, a.s->step_stride, a.s->env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "dx0", p->dx0.ptr, true, 1, B, nx, 0, p->dx0.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "alphas", p->alphas, false, 1, 1, na, 0, 0)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "lo", p->lo, true, 1, 1, nu, 0, 0)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "hi", p->hi, true, 1, 1, nu, 0, 0)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "cand", p->cand, false, 1, B, na * T * nu, 0, na * T * nu, p->out_f32 ? 4 : 8)) != MJB_OK) return rc;
+  LqrCandArgs a;
+  a.T = p->T; a.B = p->batch; a.nx = p->nx; a.nu = p->nu; a.nalpha = p->nalpha; a.out_f32 = p->out_f32 ? 1 : 0;
+  a.A = lqr_arr(p->A); a.Bm = lqr_arr(p->B); a.k = lqr_arr(p->k); a.K = lqr_arr(p->K); a.u = lqr_arr(p->u); a.dx0 = lqr_arr(p->dx0);
+  a.alphas = p->alphas; a.lo = p->lo; a.hi = p->hi; a.cand = p->cand;
+  const hipError_t e = lqr_launch_candidates(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_candidates launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+int mjb_lqr_gemm_tn(mjbData* d, int M, int N, int K, const double* a, const double* b, double* c) {
+  static const char* fn = "mjb_lqr_gemm_tn";
+  if (!d) return fail(MJB_ERR_ARG, "mjb_lqr_gemm_tn: data is NULL");
+  if (M < 1 || N < 1 || K < 1 || M > kLqrMaxNx || N > kLqrMaxNx || K > (1 << 20)) return fail(MJB_ERR_ARG, "mjb_lqr_gemm_tn: M, N must lie in [1, 64], K in [1, 2^20]");
+  HIPCHK(hipSetDevice(d->device));
+  int rc;
+  if ((rc = check_lqr_array(d, fn, "a", a, false, 1, 1, (long)K * M, 0, 0)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "b", b, false, 1, 1, (long)K * N, 0, 0)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "c", c, false, 1, 1, (long)M * N, 0, 0)) != MJB_OK) return rc;
+  const hipError_t e = lqr_launch_gemm_probe(M, N, K, a, b, c, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_gemm_tn launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
 
 int mjb_transition_fd(mjbData* d, double eps, int centered, double* A_host, double* B_host) {
   if (!d || !A_host || !B_host) return fail(MJB_ERR_ARG, "NULL argument");

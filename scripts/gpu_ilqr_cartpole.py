@@ -2,14 +2,16 @@
 
 Each iteration (horizon T, one nominal control sequence):
   linearise  ``linearize_rollout`` - the nominal rollout and (A_t, B_t) at every step of it, two submissions;
-  backward   the Riccati recursion in torch float64 on the GPU -> feed-forward k_t and gains K_t;
+  backward   the Riccati recursion -> feed-forward k_t and gains K_t: ``lqr_backward``, one kernel launch (--backward kernel, the
+             default), or the loop of small torch float64 operations it replaces (--backward torch);
   forward    a line search over --alphas step sizes as ONE ``rollout`` (one environment per alpha).  The rollout is open loop, so
              the candidate controls come from the closed loop run on the LINEARISED dynamics: dx' = A dx + B du,
-             du = alpha k + K dx; the true cost of each candidate is evaluated on the simulated states and the best one is kept.
+             du = alpha k + K dx (``lqr_candidates``, one launch; with --backward torch a second torch loop); the true cost of each
+             candidate is evaluated on the simulated states and the best one is kept.
 The pole starts tilted by --tilt rad; the cost asks for the upright pole at the origin.  Prints one JSON line: cost per iteration,
 the tilt at the end of the final trajectory and the wall time of each phase (each closed by a device synchronise).
 
-    python scripts/gpu_ilqr_cartpole.py [--horizon 100] [--iters 15] [--alphas 16] [--tilt 0.3] [--out FILE.json]
+    python scripts/gpu_ilqr_cartpole.py [--horizon 100] [--iters 15] [--alphas 16] [--tilt 0.3] [--backward kernel|torch] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from mujoco_template_amd import linearize_rollout, mj, rollout  # noqa: E402
+from mujoco_template_amd import linearize_rollout, lqr_backward, lqr_candidates, mj, rollout  # noqa: E402
 
 XML = os.path.join(ROOT, "models", "cartpole.xml")
 U_MAX = 4.0
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--alphas", type=int, default=16)
     ap.add_argument("--tilt", type=float, default=0.3)
+    ap.add_argument("--backward", choices=("kernel", "torch"), default="kernel")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -70,25 +73,35 @@ def main():
         t1 = time.perf_counter()
         costs.append(float(cost(state, u)[0]))
         xs = torch.cat([x0[1:].to(dev)[None], state[0, :, 1:]])                # [T + 1, nx]: x_t before step t, x_T the last state
-        A, Bm = A[0], Bm[0]
-        Vx, Vxx = Qf @ xs[T], Qf.clone()
-        ks, Ks = torch.zeros((T, nu), dtype=f64, device=dev), torch.zeros((T, nu, nx), dtype=f64, device=dev)
-        for t in range(T - 1, -1, -1):
-            lx = Q @ xs[t] if t > 0 else torch.zeros(nx, dtype=f64, device=dev)
-            Qx, Qu = lx + A[t].T @ Vx, R @ u[0, t] + Bm[t].T @ Vx
-            Qxx, Quu, Qux = (Q if t > 0 else 0 * Q) + A[t].T @ Vxx @ A[t], R + Bm[t].T @ Vxx @ Bm[t] + reg * torch.eye(nu, dtype=f64, device=dev), Bm[t].T @ Vxx @ A[t]
-            ks[t], Ks[t] = -torch.linalg.solve(Quu, Qu), -torch.linalg.solve(Quu, Qux)
-            Vx = Qx + Ks[t].T @ Quu @ ks[t] + Ks[t].T @ Qu + Qux.T @ ks[t]
-            Vxx = Qxx + Ks[t].T @ Quu @ Ks[t] + Ks[t].T @ Qux + Qux.T @ Ks[t]
-            Vxx = 0.5 * (Vxx + Vxx.T)
+        if args.backward == "kernel":
+            lx = (xs[:T] @ Q).clone()
+            lx[0] = 0                                                          # the script's cost has no state term at t = 0
+            lxx = Q.expand(T, nx, nx).clone()
+            lxx[0] = 0
+            sol = lqr_backward(nominal, A, Bm, lx=lx[None], lu=u @ R, lxx=lxx[None], luu=R, VxT=Qf @ xs[T], VxxT=Qf, mu=reg)
+        else:
+            A, Bm = A[0], Bm[0]
+            Vx, Vxx = Qf @ xs[T], Qf.clone()
+            ks, Ks = torch.zeros((T, nu), dtype=f64, device=dev), torch.zeros((T, nu, nx), dtype=f64, device=dev)
+            for t in range(T - 1, -1, -1):
+                lx = Q @ xs[t] if t > 0 else torch.zeros(nx, dtype=f64, device=dev)
+                Qx, Qu = lx + A[t].T @ Vx, R @ u[0, t] + Bm[t].T @ Vx
+                Qxx, Quu, Qux = (Q if t > 0 else 0 * Q) + A[t].T @ Vxx @ A[t], R + Bm[t].T @ Vxx @ Bm[t] + reg * torch.eye(nu, dtype=f64, device=dev), Bm[t].T @ Vxx @ A[t]
+                ks[t], Ks[t] = -torch.linalg.solve(Quu, Qu), -torch.linalg.solve(Quu, Qux)
+                Vx = Qx + Ks[t].T @ Quu @ ks[t] + Ks[t].T @ Qu + Qux.T @ ks[t]
+                Vxx = Qxx + Ks[t].T @ Quu @ Ks[t] + Ks[t].T @ Qux + Qux.T @ Ks[t]
+                Vxx = 0.5 * (Vxx + Vxx.T)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        dx = torch.zeros((K, nx), dtype=f64, device=dev)                       # closed loop on the linearised dynamics, all alphas at once
-        cand = torch.empty((K, T, nu), dtype=f64, device=dev)
-        for t in range(T):
-            du = alphas[:, None] * ks[t][None] + dx @ Ks[t].T
-            cand[:, t] = (u[0, t][None] + du).clamp(-U_MAX, U_MAX)
-            dx = dx @ A[t].T + (cand[:, t] - u[0, t][None]) @ Bm[t].T
+        if args.backward == "kernel":
+            cand = lqr_candidates(nominal, A, Bm, sol.k, sol.K, u, alphas, lo=-U_MAX, hi=U_MAX)[0]
+        else:
+            dx = torch.zeros((K, nx), dtype=f64, device=dev)                       # closed loop on the linearised dynamics, all alphas at once
+            cand = torch.empty((K, T, nu), dtype=f64, device=dev)
+            for t in range(T):
+                du = alphas[:, None] * ks[t][None] + dx @ Ks[t].T
+                cand[:, t] = (u[0, t][None] + du).clamp(-U_MAX, U_MAX)
+                dx = dx @ A[t].T + (cand[:, t] - u[0, t][None]) @ Bm[t].T
         st, _ = rollout(model, search, cand, initial_state=x0)
         c = cost(st, cand)
         best = int(torch.argmin(torch.nan_to_num(c, nan=float("inf"))))
@@ -98,7 +111,7 @@ def main():
         split["linearise"] += t1 - t0; split["backward"] += t2 - t1; split["forward"] += t3 - t2
     state, _ = rollout(model, nominal, u, initial_state=x0)
     costs.append(float(cost(state, u)[0]))
-    res = {"horizon": T, "iterations": args.iters, "alphas": K, "tilt0_rad": args.tilt, "cost_per_iteration": costs,
+    res = {"backward": args.backward, "horizon": T, "iterations": args.iters, "alphas": K, "tilt0_rad": args.tilt, "cost_per_iteration": costs,
            "final_tilt_rad": float(state[0, -1, 2]), "final_slider_m": float(state[0, -1, 1]),
            "wall_s": {k: v for k, v in split.items()}, "wall_share": {k: v / sum(split.values()) for k, v in split.items()}}
     print(json.dumps(res), flush=True)
