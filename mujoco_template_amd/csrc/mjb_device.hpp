@@ -143,6 +143,15 @@ template <int G> MJB_DEV int gscan_small(int v, int lane, int& total) {
   total = tot;
   return pre;
 }
+// sum over the group of SMALL counts (0 <= v < 8): the ballots of gscan_small with population counts of whole masks only
+template <int G> MJB_DEV int gtotal_small(int v, int lane) {
+  const int wl = (int)(threadIdx.x & 63);
+  const unsigned long long gm = G == 64 ? ~0ull : (((1ull << (G & 63)) - 1ull) << (wl - lane));
+  int tot = 0;
+#pragma unroll
+  for (int b = 0; b < 3; b++) tot += __popcll(__ballot((v >> b) & 1) & gm) << b;
+  return tot;
+}
 template <int G> MJB_DEV int gscan_excl(int v, int lane, int& total) {
   int x = v;
 #pragma unroll
@@ -1498,27 +1507,42 @@ template <typename T, int G> MJB_DEV void com_pos(Ctx<T>& c) {
       cd[0] = ax[0]; cd[1] = ax[1]; cd[2] = ax[2]; cd[3] = cr[0]; cd[4] = cr[1]; cd[5] = cr[2];
     }
   }
-  // fixed tendons: length and Jacobian
-  T *tl = w + L.ten_length, *tj = w + L.ten_J, *qpos = w + L.qpos;
+  // fixed tendons: length (their Jacobian holds model constants only: tendon_jacobian, once per launch)
+  T *tl = w + L.ten_length, *qpos = w + L.qpos;
   for (int t = lane; t < m.ntendon; t += G) {
-    for (int i = 0; i < m.nv; i++) tj[t * m.nv + i] = 0;
     T len = 0;
     for (int wi = m.tendon_adr[t]; wi < m.tendon_adr[t] + m.tendon_num[t]; wi++) {
       int j = m.wrap_objid[wi];
       len += m.wrap_prm[wi] * qpos[m.jnt_qposadr[j]];
-      tj[t * m.nv + m.jnt_dofadr[j]] = m.wrap_prm[wi];
     }
     tl[t] = len;
   }
   gsync<G>();
 }
 
+// Jacobian of the fixed tendons: the wrap coefficients at the dofs of their joints, zero elsewhere.  Model constants in a part of the
+// LDS slice that no phase overlays (make_layout), so the kernels write it once, where they clear M, before their step loop; the
+// caller's next gsync publishes it.
+template <typename T, int G> MJB_DEV void tendon_jacobian(Ctx<T>& c) {
+  MJB_ENV(c); T* tj = c.w + L.ten_J;
+  for (int t = c.lane; t < m.ntendon; t += G) {
+    for (int i = 0; i < m.nv; i++) tj[t * m.nv + i] = 0;
+    for (int wi = m.tendon_adr[t]; wi < m.tendon_adr[t] + m.tendon_num[t]; wi++) tj[t * m.nv + m.jnt_dofadr[m.wrap_objid[wi]]] = m.wrap_prm[wi];
+  }
+}
+
 // Jacobian column of dof i for a world point attached to body b (zero if i does not move b)
+template <typename T> MJB_DEV void jac_col_moving(const Ctx<T>& c, int b, int i, const T* point, T* jp, T* jr);
 template <typename T> MJB_DEV void jac_col(const Ctx<T>& c, int b, int i, const T* point, T* jp, T* jr) {
   ModelRef<T> m = MJB_MODEL_OF(c.mp);
   jp[0] = jp[1] = jp[2] = 0;
   if (jr) { jr[0] = jr[1] = jr[2] = 0; }
   if (!((m.body_dofmask[b] >> i) & 1ull)) return;
+  jac_col_moving<T>(c, b, i, point, jp, jr);
+}
+// the column itself, for a dof i that is known to move body b (bit i of body_dofmask[b])
+template <typename T> MJB_DEV void jac_col_moving(const Ctx<T>& c, int b, int i, const T* point, T* jp, T* jr) {
+  ModelRef<T> m = MJB_MODEL_OF(c.mp);
   const T* cd = c.w + c.lp->cdof + 6 * i;
   const T* sc = c.w + c.lp->subtree_com + 3 * m.body_rootid[b];
   T off[3] = {point[0] - sc[0], point[1] - sc[1], point[2] - sc[2]}, ang[3] = {cd[0], cd[1], cd[2]}, t[3];
@@ -1780,10 +1804,11 @@ template <typename T, int G> MJB_DEV void collision(Ctx<T>& c) {
 // ---------------------------------------------------------------------------
 // A6 constraint rows: limits + contacts; impedance, R/D, Jacobian, aref
 // ---------------------------------------------------------------------------
-// impedance and regulariser of one row (the state-dependent half of row_params; K and B are host-folded model constants)
+// impedance and regulariser of one row (the state-dependent half of row_params; K and B are host-folded model constants).
+// `solimp` is the CLAMPED (dmin, dmax, width, mid, power) of the host-built records (lim_f, pair_kb: fill_dev_model clamps after the
+// cast to T with the min / max row_params applies, which are exact)
 template <typename T> MJB_DEV void row_imp_R(T pos, T margin, const T* solimp, T diagApprox, T& imp, T& R) {
-  T dmin = t_min(t_max(solimp[0], MJB_MINIMP), MJB_MAXIMP), dmax = t_min(t_max(solimp[1], MJB_MINIMP), MJB_MAXIMP);
-  T width = t_max(solimp[2], (T)0), mid = t_min(t_max(solimp[3], MJB_MINIMP), MJB_MAXIMP), power = t_max(solimp[4], (T)1);
+  const T dmin = solimp[0], dmax = solimp[1], width = solimp[2], mid = solimp[3], power = solimp[4];
   if (dmin == dmax || width <= Num<T>::minval()) imp = (T)0.5 * (dmin + dmax);
   else {
     T x = t_abs(pos - margin) / width;
@@ -1843,85 +1868,97 @@ template <typename T, int G> MJB_DEV void make_constraint(Ctx<T>& c) {
   T *emargin = w + L.efc_KBI;
   int *etype = c.wi + L.i_efc_type, *con_pair = c.wi + L.i_con_pair;   // etype: bits 0-7 type, 8 active-at-last-factor, 9.. object id
   T *con = w + L.con, *tl = w + L.ten_length, *tj = w + L.ten_J;
-  int nefc = 0, dropped = 0;
-  // joint limits, then tendon limits, in ONE lane-parallel pass over the njnt + ntendon objects (rows keep that order):
-  // object `o`, side 0 (lower) then 1 (upper)
-  {
-    const int nobj = m.njnt + m.ntendon;
-    for (int base = 0; base < nobj; base += G) {
-      const int k = base + lane;
-      const bool isj = k < m.njnt;
-      const int o = isj ? k : k - m.njnt;
-      int cnt = 0;
-      T dist[2] = {0, 0}, margin = 0;
-      bool act[2] = {false, false};
-      T rec[12];
-      if (k < nobj && m.lim_i[2 * k]) {                         // one record per limit object: no index hops
-        const int vi = m.lim_i[2 * k + 1];
-#pragma unroll
-        for (int q = 0; q < 11; q++) rec[q] = m.lim_f[12 * k + q];
-        T value = isj ? qpos[vi] : tl[vi];
-        margin = rec[2];
-        dist[0] = value - rec[0]; dist[1] = rec[1] - value;
-        act[0] = dist[0] < margin; act[1] = dist[1] < margin;
-        cnt = (int)act[0] + (int)act[1];
+  // ONE lane-parallel pass over the items [njnt + ntendon limit objects | ncon contacts] (in chunks of G, carried row counts): one
+  // prefix scan of the row counts (limit object 0 / 1 / 2: lower side, then upper; contact 0 / 1 / 4) and one instance of the
+  // impedance code per lane.  Rows keep the order limit objects, then contacts.  Caps: limit rows at and beyond `cap` are dropped one
+  // by one; the contact block starts at min(limit rows, cap); a contact is placed only if all its rows fit.
+  const int nobj = m.njnt + m.ntendon, nitem = nobj + c.ncon;
+  int nlim = 0, ncrow = 0;                                      // limit rows / contact rows so far, uncapped
+  for (int base = 0; base < nitem; base += G) {
+    const int k = base + lane;
+    const bool isl = k < nobj, isj = k < m.njnt;
+    const int ci = k - nobj;
+    int cnt = 0, p = 0, sd = 0;
+    T dist = 0, dist2 = 0, margin = 0, mu = 0;
+    bool both = false;
+    if (isl) {
+      if (m.lim_i[2 * k]) {                                     // one record per limit object: no index hops
+        const T value = isj ? qpos[m.lim_i[2 * k + 1]] : tl[m.lim_i[2 * k + 1]];
+        margin = m.lim_f[12 * k + 2];
+        const T d0 = value - m.lim_f[12 * k], d1 = m.lim_f[12 * k + 1] - value;
+        const bool a0 = d0 < margin, a1 = d1 < margin;
+        cnt = (int)a0 + (int)a1;
+        both = a0 && a1;                                        // only where the range is narrower than twice the margin
+        dist = a0 ? d0 : d1; dist2 = d1; sd = a0 ? 0 : 1;       // the first (or only) active side; the upper side follows where both are
       }
-      int total, off = gscan_small<G>(cnt, lane, total);
-      int row = nefc + off;
-      if (cnt > 0) {
-#pragma unroll
-        for (int sd = 0; sd < 2; sd++) {
-          if (act[sd]) {
-            if (row < cap) {
-              T imp, R;
-              row_imp_R(dist[sd], margin, rec + 6, rec[3], imp, R);
-              etype[row] = (isj ? EFC_LIMIT_JOINT : EFC_LIMIT_TENDON) | ((o * 2 + sd) << 9);
-              epos[row] = dist[sd]; emargin[row] = margin; eD[row] = 1 / R; eK[row] = rec[4]; eB[row] = rec[5]; eI[row] = imp;
-            }
-            row++;
-          }
-        }
-      }
-      int newn = nefc + total;
-      if (newn > cap) dropped += newn - (nefc > cap ? nefc : cap);
-      nefc = newn;
-    }
-  }
-  if (nefc > cap) nefc = cap;
-  int nlimit = nefc;
-  for (int base = 0; base < c.ncon; base += G) {
-    int ci = base + lane, rows = 0, p = 0;
-    T dist = 0, mu = 0, incm = 0;
-    if (ci < c.ncon) {
+    } else if (k < nitem) {
       p = con_pair[ci] & 0xffff;
       dist = con[ci * CON_STRIDE]; mu = con[ci * CON_STRIDE + 10];
-      incm = m.pair_kb[4 * p];
-      if (dist < incm) rows = m.pair_condim[p] == 1 ? 1 : 4;
+      margin = m.pair_kb[PAIR_KB_STRIDE * p];
+      if (dist < margin) cnt = m.pair_condim[p] == 1 ? 1 : 4;
     }
-    int total, off = gscan_small<G>(rows, lane, total);
-    int row = nefc + off;
-    if (ci < c.ncon) {
-      bool fits = rows > 0 && row + rows <= cap;
-      con_pair[ci] = p | ((fits ? row + 1 : 0) << 16);     // bits 16..: first constraint row + 1 (0 = none)
-      if (fits) {
-        const T tran = m.pair_kb[4 * p + 1], K = m.pair_kb[4 * p + 2], B = m.pair_kb[4 * p + 3];
-        T si[5] = {m.pair_solimp[5 * p], m.pair_solimp[5 * p + 1], m.pair_solimp[5 * p + 2], m.pair_solimp[5 * p + 3], m.pair_solimp[5 * p + 4]};
-        T imp, R;
-        if (rows == 1) row_imp_R(dist, incm, si, tran, imp, R);
-        else {
-          row_imp_R(dist, incm, si, tran + mu * mu * tran, imp, R);
-          R = t_max(Num<T>::minval(), 2 * mu * mu * R);
-        }
-        for (int r = 0; r < rows; r++) {
-          etype[row + r] = (rows == 1 ? EFC_CONTACT_FRICTIONLESS : EFC_CONTACT_PYRAMIDAL) | (ci << 9);
-          epos[row + r] = dist; emargin[row + r] = incm; eD[row + r] = 1 / R; eK[row + r] = K; eB[row + r] = B; eI[row + r] = imp;
-        }
+    int total, off = gscan_small<G>(cnt, lane, total);
+    const int limtot = base < nobj ? gtotal_small<G>(isl ? cnt : 0, lane) : 0;    // limit rows of this chunk: they precede its contact rows
+    const int cbase = nlim + limtot < cap ? nlim + limtot : cap;                  // first row of the contact block
+    const int row = isl ? nlim + off : cbase + ncrow + (off - limtot);
+    // the row parameters of this lane's item (the tail of the record only where a row is made)
+    bool emit = false;
+    int type = 0;
+    T diag = 0, K = 0, B = 0, si[5];
+    if (isl) {
+      if (cnt > 0) {
+        emit = row < cap;
+        type = (isj ? EFC_LIMIT_JOINT : EFC_LIMIT_TENDON) | (((isj ? k : k - m.njnt) * 2 + sd) << 9);
+      }
+      if (emit || both) {
+        diag = m.lim_f[12 * k + 3]; K = m.lim_f[12 * k + 4]; B = m.lim_f[12 * k + 5];
+#pragma unroll
+        for (int q = 0; q < 5; q++) si[q] = m.lim_f[12 * k + 6 + q];
+      }
+    } else if (k < nitem) {
+      emit = cnt > 0 && row + cnt <= cap;
+      con_pair[ci] = p | ((emit ? row + 1 : 0) << 16);          // bits 16..: first constraint row + 1 (0 = none)
+      if (emit) {
+        const T tran = m.pair_kb[PAIR_KB_STRIDE * p + 1];
+        K = m.pair_kb[PAIR_KB_STRIDE * p + 2]; B = m.pair_kb[PAIR_KB_STRIDE * p + 3];
+#pragma unroll
+        for (int q = 0; q < 5; q++) si[q] = m.pair_kb[PAIR_KB_STRIDE * p + 4 + q];
+        if (cnt == 1) diag = tran; else diag = tran + mu * mu * tran;
+        type = (cnt == 1 ? EFC_CONTACT_FRICTIONLESS : EFC_CONTACT_PYRAMIDAL) | (ci << 9);
       }
     }
-    int newn = nefc + total;
-    if (newn > cap) dropped += newn - (nefc > cap ? nefc : cap);
-    nefc = newn;
+    if (emit) {
+      T imp, R;
+      row_imp_R(dist, margin, si, diag, imp, R);
+      int nr = 1;
+      if (!isl && cnt == 4) {
+        R = t_max(Num<T>::minval(), 2 * mu * mu * R);
+        nr = 4;
+        // second tangent of the contact frame, once per contact: parked in the contact's own (not yet written) aref rows for the
+        // Jacobian loop below
+        const T* cc = con + ci * CON_STRIDE;
+        T nrm[3] = {cc[4], cc[5], cc[6]}, t1[3] = {cc[7], cc[8], cc[9]}, t2[3];
+        cross3(t2, nrm, t1);
+        earef[row] = t2[0]; earef[row + 1] = t2[1]; earef[row + 2] = t2[2];
+      }
+      for (int r = 0; r < nr; r++) {
+        etype[row + r] = type;
+        epos[row + r] = dist; emargin[row + r] = margin; eD[row + r] = 1 / R; eK[row + r] = K; eB[row + r] = B; eI[row + r] = imp;
+      }
+    }
+    if (base < nobj && gany<G>(both)) {                         // the upper side of a limit object with both sides active: a second trip
+      if (both && row + 1 < cap) {
+        T imp, R;
+        row_imp_R(dist2, margin, si, diag, imp, R);
+        etype[row + 1] = type + (1 << 9);
+        epos[row + 1] = dist2; emargin[row + 1] = margin; eD[row + 1] = 1 / R; eK[row + 1] = K; eB[row + 1] = B; eI[row + 1] = imp;
+      }
+    }
+    nlim += limtot; ncrow += total - limtot;
   }
+  const int nlimit = nlim < cap ? nlim : cap;
+  int nefc = nlimit + ncrow;
+  const int dropped = (nlim > cap ? nlim - cap : 0) + (nefc > cap ? nefc - cap : 0);
   // contacts that did not fit leave holes only at the tail: rows are contiguous because offsets are monotone
   if (nefc > cap) {
     // recompute the true count = last fitting contact's end
@@ -1958,15 +1995,20 @@ template <typename T, int G> MJB_DEV void make_constraint(Ctx<T>& c) {
       int p = con_pair[ci] & 0xffff;
       int b1 = m.pair_body[2 * p], b2 = m.pair_body[2 * p + 1];
       const T* cc = con + ci * CON_STRIDE;
-      T pos[3] = {cc[1], cc[2], cc[3]}, j1[3], j2[3], dj[3];
-      jac_col<T>(c, b1, i, pos, j1, (T*)0);
-      jac_col<T>(c, b2, i, pos, j2, (T*)0);
-      dj[0] = j2[0] - j1[0]; dj[1] = j2[1] - j1[1]; dj[2] = j2[2] - j1[2];
+      // column of body 2 minus column of body 1: a dof that moves both (the same column twice) or neither gives exactly +0, a dof
+      // that moves one of them gives that body's column, as +col - 0 or 0 - col
+      const bool mv1 = (m.body_dofmask[b1] >> i) & 1ull, mv2 = (m.body_dofmask[b2] >> i) & 1ull;
+      T dj[3] = {0, 0, 0};
+      if (mv1 != mv2) {
+        T pos[3] = {cc[1], cc[2], cc[3]}, col[3];
+        jac_col_moving<T>(c, mv2 ? b2 : b1, i, pos, col, (T*)0);
+        if (mv2) { dj[0] = col[0]; dj[1] = col[1]; dj[2] = col[2]; }
+        else { dj[0] = (T)0 - col[0]; dj[1] = (T)0 - col[1]; dj[2] = (T)0 - col[2]; }
+      }
       T jn = cc[4] * dj[0] + cc[5] * dj[1] + cc[6] * dj[2];
       if (m.pair_condim[p] == 1) J[row * nv + i] = jn;
       else {
-        T mu = cc[10], nrm[3] = {cc[4], cc[5], cc[6]}, t1[3] = {cc[7], cc[8], cc[9]}, t2[3];
-        cross3(t2, nrm, t1);
+        T mu = cc[10], t1[3] = {cc[7], cc[8], cc[9]}, t2[3] = {earef[row], earef[row + 1], earef[row + 2]};
         T jt1 = mu * dot3(t1, dj), jt2 = mu * dot3(t2, dj);
         J[row * nv + i] = jn + jt1; J[(row + 1) * nv + i] = jn - jt1;
         J[(row + 2) * nv + i] = jn + jt2; J[(row + 3) * nv + i] = jn - jt2;
@@ -2911,6 +2953,7 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
   }
   for (int i = lane; i < nu; i += G) w[L.ctrl + i] = a.ctrl_mode == CTRL_ZERO ? (T)0 : (T)d.ctrl[(size_t)env * nu + i];
   for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;       // structural zeros of the mass matrix (crb_factor fills the rest)
+  tendon_jacobian<T, G>(c);
 #ifndef MJB_HOST_EMU
   if (a.mirror && a.mirror_mask) mirror_in<T, G>(m, L, w, a.mirror, a.mirror_mask, env, d.batch, lane, time);
 #endif
@@ -3094,6 +3137,7 @@ MJB_DEV void env_run2(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, 
     }
     for (int i = lane; i < nu; i += G) w[L.ctrl + i] = a.ctrl_mode == CTRL_ZERO ? (T)0 : (T)d.ctrl[(size_t)env * nu + i];
     for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;     // structural zeros of the mass matrix
+    tendon_jacobian<T, G>(c);
     if (lane < 8) mail[lane] = 0;
     time = d.time[env];
     if (a.mirror && a.mirror_mask) mirror_in<T, G>(m, L, w, a.mirror, a.mirror_mask, env, d.batch, lane, time);

@@ -270,13 +270,24 @@ void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max
     const auto& g1 = h.I("pair_geom1"); const auto& g2 = h.I("pair_geom2"); const auto& gb = h.I("geom_bodyid");
     const auto& pm = h.D("pair_margin"); const auto& pg = h.D("pair_gap"); const auto& psr = h.D("pair_solref"); const auto& psi = h.D("pair_solimp");
     const auto& biw = h.D("body_invweight0");
-    std::vector<T> kb((size_t)h.npair * 4);
+    // solimp as row_imp_R reads it: clamped AFTER the cast to T, with the comparisons row_params applies to the raw values (a > b ? a : b
+    // selects one of its operands: exact), so the device finds the bits it used to compute from the raw values
+    auto clamp_solimp = [](const double* raw, T* out) {
+      const T lo = (T)0.0001, hi = (T)0.9999;                  // MJB_MINIMP, MJB_MAXIMP
+      auto tmax = [](T a, T b) { return a > b ? a : b; };
+      auto tmin = [](T a, T b) { return a < b ? a : b; };
+      out[0] = tmin(tmax((T)raw[0], lo), hi); out[1] = tmin(tmax((T)raw[1], lo), hi);
+      out[2] = tmax((T)raw[2], (T)0); out[3] = tmin(tmax((T)raw[3], lo), hi); out[4] = tmax((T)raw[4], (T)1);
+    };
+    std::vector<T> kb((size_t)h.npair * PAIR_KB_STRIDE, (T)0);
     for (int p = 0; p < h.npair; p++) {
       double K, B;
       KB(&psr[2 * p], psi[5 * p + 1], K, B);
-      kb[4 * p] = (T)(pm[p] - pg[p]);
-      kb[4 * p + 1] = (T)(biw[2 * gb[g1[p]]] + biw[2 * gb[g2[p]]]);
-      kb[4 * p + 2] = (T)K; kb[4 * p + 3] = (T)B;
+      T* r = &kb[(size_t)p * PAIR_KB_STRIDE];
+      r[0] = (T)(pm[p] - pg[p]);
+      r[1] = (T)(biw[2 * gb[g1[p]]] + biw[2 * gb[g2[p]]]);
+      r[2] = (T)K; r[3] = (T)B;
+      clamp_solimp(&psi[5 * p], r + 4);
     }
     m.pair_kb = (FP)alloc.putf(kb);
     std::vector<int> pb((size_t)h.npair * 2);
@@ -293,7 +304,7 @@ void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max
       KB(&jsr[2 * o], jsi[5 * o + 1], K, B);
       T* r = &lf[(size_t)o * 12];
       r[0] = (T)jr[2 * o]; r[1] = (T)jr[2 * o + 1]; r[2] = (T)jm[o]; r[3] = (T)diw[jd[o]]; r[4] = (T)K; r[5] = (T)B;
-      for (int k = 0; k < 5; k++) r[6 + k] = (T)jsi[5 * o + k];
+      clamp_solimp(&jsi[5 * o], r + 6);
       li[2 * o] = (jl[o] && (jt[o] == JNT_HINGE || jt[o] == JNT_SLIDE)) ? 1 : 0; li[2 * o + 1] = jq[o];
     }
     if (h.ntendon > 0) {
@@ -304,7 +315,7 @@ void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max
         KB(&tsr[2 * t], tsi[5 * t + 1], K, B);
         T* r = &lf[(size_t)(h.njnt + t) * 12];
         r[0] = (T)tr[2 * t]; r[1] = (T)tr[2 * t + 1]; r[2] = (T)tm[t]; r[3] = (T)tiw[t]; r[4] = (T)K; r[5] = (T)B;
-        for (int k = 0; k < 5; k++) r[6 + k] = (T)tsi[5 * t + k];
+        clamp_solimp(&tsi[5 * t], r + 6);
         li[2 * (h.njnt + t)] = tl[t] != 0 ? 1 : 0; li[2 * (h.njnt + t) + 1] = t;
       }
     }

@@ -65,6 +65,7 @@ template <int G> static inline int gscan_excl(int v, int lane, int& total) {
   return (int)s;
 }
 template <int G> static inline int gscan_small(int v, int lane, int& total) { return gscan_excl<G>(v, lane, total); }
+template <int G> static inline int gtotal_small(int v, int) { return gsumi<G>(v); }
 // ---- wave-level intrinsics of the fp32 hot path (one wavefront per environment: readlane, the 32-lane half swap, ballot and the
 // 32x32x2 fp32 MFMA) so that the CPU suite executes the MFMA Cholesky / sweep-inverse code itself, not a substitute path.  Every
 // call is a collective of all G lane-threads; values go through double-buffered scratch so that ONE barrier per call suffices (a

@@ -207,6 +207,7 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
   int* wi = (int*)(w + L.nT);
   Ctx<T> c(mp, lp, w, wi, lane, kernarg_prm<T, TS>(), env);
   for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;       // structural zeros of the mass matrix (crb_factor fills the rest)
+  tendon_jacobian<T, G>(c);                                     // also for the jobs that skip the position stage
   const int nstage = rk4 ? 4 : 1;
   for (int it = share > 0 ? -1 : 0; it < cnt; it++) {           // it = -1: the shared stages at the nominal state
     {                                                           // the point's rows: every column restarts from the same state and warm start

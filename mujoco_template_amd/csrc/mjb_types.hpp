@@ -65,8 +65,8 @@ struct DevModel {
   // collision pairs
   IP pair_geom1, pair_geom2, pair_condim;
   FP pair_friction, pair_solref, pair_solimp, pair_margin, pair_gap;
-  FP pair_kb;        // per pair: margin - gap, body_invweight0 sum (translational), K, B of the contact rows (all model constants)
-  FP lim_f;          // per limit object (joints, then tendons) x 12: range lo/hi, margin, diagApprox, K, B, solimp[5], pad
+  FP pair_kb;        // per pair x PAIR_KB_STRIDE: margin - gap, body_invweight0 sum (translational), K, B of the contact rows, clamped solimp[5], pad
+  FP lim_f;          // per limit object (joints, then tendons) x 12: range lo/hi, margin, diagApprox, K, B, clamped solimp[5], pad
   FP jnt_rec;        // per joint x 8: jnt_pos[3], jnt_axis[3], qpos0[jnt_qposadr], pad   (kinematics: one record, no second hop)
   IP jnt_irec;       // per joint x 6: type, qposadr, dofadr, body, parent of that body, root of that body
   IP dof_irec;       // per dof x 6: body, parent of that body, first dof of the body, dof where its velocity group starts (-1: translational dof of a free joint), qpos address of its spring (-1: none), pad
@@ -99,6 +99,7 @@ struct Lay {
   int bytes;          // total bytes per environment (rounded to 16)
 };
 
+constexpr int PAIR_KB_STRIDE = 12;
 constexpr int CON_STRIDE = 11;  // dist, pos[3], normal[3], tangent1[3], mu (friction[0]); tangent2 = n x t1; pair id in i_con_pair
 
 // Per-environment model parameters (mjb_set_env_param): slot k holds the [batch, n_k] rows of field k in both precisions, or null
