@@ -359,6 +359,66 @@ int mjb_lqr_candidates(mjbData* d, const mjbLqrCandidates* p);
  * above alone: a diagnostic that pins the operand and result fragment maps of v_mfma_f64_16x16x4_f64 with exact integer data. */
 int mjb_lqr_gemm_tn(mjbData* d, int M, int N, int K, const double* a, const double* b, double* c);
 
+/* ---- the quadratic trajectory cost, its first-order expansion and the choice among candidates: what an iLQR iteration or a sampling
+ * planner needs between mjb_rollout_ctrl / mjb_transition_fd_points and mjb_lqr_backward / mjb_lqr_candidates, on the device.  The
+ * reference's humanoid controller builds its Q in the 2nv tangent space (examples/humanoid/controllers/lqr.py:97-114) and takes the
+ * state difference with mj_differentiatePos (examples/humanoid/controllers/lqr.py:153); this is that cost along whole trajectories.
+ *
+ * A trajectory e has T + 1 points: x_0 the start state, x_{t+1} the state after step t.  For point t, in float64, inputs widened exactly:
+ *   dx_t = [ differentiatePos(qref_t -> qpos_t, dt = 1) ; qvel_t - vref_t ]     (2nv; sign and quaternion rule of
+ *                                                                                 mjb_differentiate_pos(qvel_out, 1, qref, qpos))
+ *   du_t = u_t - uref_t
+ *   cost_t[e, t] = dx_t' Q_t dx_t / 2 + du_t' R_t du_t / 2    (t < T),     cost_t[e, T] = dx_T' Qf dx_T / 2
+ *   cost[e] = sum_t cost_t[e, t]; a sum that is NaN or infinite is stored as +inf (cost is never NaN)
+ *   lx[t, e] = Q_t dx_t, lu[t, e] = R_t du_t (t < T), VxT[e] = Qf dx_T   - what mjb_lqr_backward takes (lxx = Q, luu = R, VxxT = Qf are
+ *   the caller's own arrays).  Q, R, Qf are TAKEN AS SYMMETRIC, not checked: the kernel reads Q[j, i] for Q[i, j].
+ * Inputs, all (ptr, step_stride, env_stride) arrays as above (strides in elements, >= 0, 0 = broadcast):
+ *   qpos0 [nq], qvel0 [nv] per e (step_stride ignored); qpos [nq], qvel [nv] per (t, e), t = 0 .. T-1: the state AFTER step t - two
+ *   pointers, so the columns of a rollout ring [T, batch, dim] are read in place; ctrl [nu] per (t, e).  These carry a dtype (MJB_F32 /
+ *   MJB_F64): the four state arrays must agree, the control has its own.
+ *   float64: qref [nq] (required - a zero quaternion is no default), vref [nv] (NULL = 0) per point t = 0 .. T; uref [nu] (NULL = 0),
+ *   Q [2nv, 2nv], R [nu, nu] per (t, e), t < T; Qf [2nv, 2nv] per e (step_stride ignored).
+ * nq, nv, nu and the joint table are the data object's model; nv <= 64, 1 <= nu <= 64, T >= 1, batch >= 1 (the call's own, not the data's).
+ * Outputs, dense float64: cost [batch], cost_t [batch, T + 1] (required: it is also the staging of the sum), and optionally
+ * (NULL = not wanted) lx [T, batch, 2nv], lu [T, batch, nu], VxT [batch, 2nv].
+ * Two kernel launches on the data's stream; no scratch, no allocation, no host copy, no synchronisation, no atomics.  cost_t and the
+ * gradient blocks of a point depend on that point's inputs and (nv, nu) alone and cost[e] is summed in an order fixed by T, so a
+ * trajectory gives bitwise the same results at any position of any batch.
+ * Checked before anything is launched (MJB_ERR_ARG with a message, outputs untouched): the sizes, strides >= 0, required pointers,
+ * device memory of the data's device (hipPointerGetAttributes), the highest element read or written inside the allocation behind
+ * each pointer (hipMemGetAddressRange). */
+typedef struct mjbStridedIn { const void* ptr; long step_stride, env_stride; int dtype; } mjbStridedIn;
+typedef struct mjbTrajCost {
+  int T, batch;
+  mjbStridedIn qpos0, qvel0, qpos, qvel, ctrl;
+  mjbStrided qref, vref, uref, Q, R, Qf;
+  double *cost, *cost_t, *lx, *lu, *VxT;
+} mjbTrajCost;
+int mjb_traj_cost(mjbData* d, const mjbTrajCost* p);
+
+/* nprob problems with ncand candidates each: cost [nprob, ncand] float64, cand [nprob, ncand, T, nu] dense in cand_dtype (what
+ * mjb_lqr_candidates writes; for a sampling planner the control tensor itself with nprob = 1), u_out [nprob, T, nu] in out_dtype.
+ * 1 <= ncand <= 2^20, nprob >= 1, T * nu <= 2^22.  best [nprob] int32, best_cost [nprob], weights [nprob, ncand]: NULL = not wanted.
+ * MJB_SELECT_ARGMIN: best[g] = the lowest index among the candidates of minimal FINITE cost, best_cost[g] its cost,
+ *   u_out[g] = cand[g, best] (equal dtypes: a bit copy; float64 -> float32 rounded once; float32 -> float64 exact).  No finite cost:
+ *   best = -1, best_cost = +inf and u_out[g] is NOT written - pass the nominal as u_out and it is kept.
+ * MJB_SELECT_SOFTMIN (the MPPI update): w_j = exp(-(c_j - c_min) / temperature) over the finite costs, 0 for the others, normalised
+ *   to sum 1; u_out[g] = sum_j w_j cand[g, j] in float64, rounded once on output; best / best_cost as above; weights the w_j
+ *   (zeros when no cost is finite, u_out then not written).  temperature > 0 is checked.
+ * One launch on the data's stream, no allocation, no synchronisation, deterministic.  Checks as for mjb_traj_cost. */
+#define MJB_SELECT_ARGMIN 0
+#define MJB_SELECT_SOFTMIN 1
+typedef struct mjbTrajSelect {
+  int nprob, ncand, T, nu, mode, cand_dtype, out_dtype;
+  double temperature;
+  const double* cost;
+  const void* cand;
+  void* u_out;
+  int* best;
+  double *best_cost, *weights;
+} mjbTrajSelect;
+int mjb_traj_select(mjbData* d, const mjbTrajSelect* p);
+
 /* ---- mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacSubtreeCom (reference jacobians.py:44-79).
  * kinds[i]: 0 site, 1 body, 2 bodycom, 3 subtreecom.  jacp/jacr host [batch, nreq, 3, nv] float64 (jacr may be NULL) ---- */
 int mjb_jac(mjbData* d, int nreq, const int* kinds, const int* ids, double* jacp_host, double* jacr_host);

@@ -56,6 +56,26 @@ class LqrCandidatesStruct(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("alphas", "lo", "hi", "cand")]
 
 
+class StridedIn(ctypes.Structure):
+    """``mjbStridedIn``: an ``mjbStrided`` array of float32 (dtype 0) or float64 (dtype 1) elements."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("step_stride", ctypes.c_long), ("env_stride", ctypes.c_long), ("dtype", ctypes.c_int)]
+
+
+class TrajCostStruct(ctypes.Structure):
+    """``mjbTrajCost`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("T", "batch")] + \
+               [(n, StridedIn) for n in ("qpos0", "qvel0", "qpos", "qvel", "ctrl")] + \
+               [(n, Strided) for n in ("qref", "vref", "uref", "Q", "R", "Qf")] + \
+               [(n, ctypes.c_void_p) for n in ("cost", "cost_t", "lx", "lu", "VxT")]
+
+
+class TrajSelectStruct(ctypes.Structure):
+    """``mjbTrajSelect`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("nprob", "ncand", "T", "nu", "mode", "cand_dtype", "out_dtype")] + \
+               [("temperature", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("cost", "cand", "u_out", "best", "best_cost", "weights")]
+
+
 def load_library() -> ctypes.CDLL:
     global _LIB
     if _LIB is not None:
@@ -131,6 +151,10 @@ def load_library() -> ctypes.CDLL:
     L.mjb_lqr_candidates.restype = ci
     L.mjb_lqr_gemm_tn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.mjb_lqr_gemm_tn.restype = ci
+    L.mjb_traj_cost.argtypes = [vp, ctypes.POINTER(TrajCostStruct)]
+    L.mjb_traj_cost.restype = ci
+    L.mjb_traj_select.argtypes = [vp, ctypes.POINTER(TrajSelectStruct)]
+    L.mjb_traj_select.restype = ci
     L.mjb_jac.argtypes = [vp, ci, vp, vp, vp, vp]
     L.mjb_profile_get.argtypes = [vp, vp]
     L.mjb_profile_get.restype = ci
@@ -990,8 +1014,8 @@ class BatchSim:
     def _lqr_call(self, fn, struct, sizes: dict, arrays: dict, pointers: dict, keep) -> None:
         for k, v in sizes.items():
             setattr(struct, k, int(v))
-        for k, (ptr, ss, es) in arrays.items():
-            setattr(struct, k, Strided(ptr or None, int(ss), int(es)))
+        for k, v in arrays.items():                                 # (address, step stride, env stride[, dtype code]): mjbStrided / mjbStridedIn
+            setattr(struct, k, Strided(v[0] or None, int(v[1]), int(v[2])) if len(v) == 3 else StridedIn(v[0] or None, int(v[1]), int(v[2]), int(v[3])))
         for k, ptr in pointers.items():
             setattr(struct, k, ptr or None)
         self.use_torch_stream()
@@ -1008,6 +1032,17 @@ class BatchSim:
     def lqr_candidates(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
         """``mjb_lqr_candidates`` on raw device addresses (see ``lqr_backward``)."""
         self._lqr_call(load_library().mjb_lqr_candidates, LqrCandidatesStruct(), sizes, arrays, pointers, keep)
+
+    def traj_cost(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_traj_cost`` on raw device addresses (see ``lqr_backward``); the state and control entries of ``arrays`` carry a
+        fourth element, the dtype code (0 float32, 1 float64).  ``trajopt.trajectory_cost`` is the checked tensor interface."""
+        self._lqr_call(load_library().mjb_traj_cost, TrajCostStruct(), sizes, arrays, pointers, keep)
+
+    def traj_select(self, sizes: dict, pointers: dict, keep=()) -> None:
+        """``mjb_traj_select`` on raw device addresses; ``sizes`` also holds mode, cand_dtype, out_dtype and temperature."""
+        struct = TrajSelectStruct()
+        struct.temperature = float(sizes.get("temperature", 0.0))
+        self._lqr_call(load_library().mjb_traj_select, struct, {k: v for k, v in sizes.items() if k != "temperature"}, {}, pointers, keep)
 
     def lqr_gemm_tn(self, a, b):
         """``a [K, M]``, ``b [K, N]`` float64 tensors on this GPU -> ``a.T @ b`` through the kernels' f64 MFMA tile product alone."""

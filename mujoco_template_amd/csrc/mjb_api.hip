@@ -18,6 +18,7 @@
 #include "mjb_host.hpp"
 #include "mjb_kernels.hpp"
 #include "mjb_lqr.hpp"
+#include "mjb_traj.hpp"
 
 using namespace mjb;
 
@@ -1716,6 +1717,95 @@ int mjb_lqr_gemm_tn(mjbData* d, int M, int N, int K, const double* a, const doub
   if ((rc = check_lqr_array(d, fn, "c", c, false, 1, 1, (long)M * N, 0, 0)) != MJB_OK) return rc;
   const hipError_t e = lqr_launch_gemm_probe(M, N, K, a, b, c, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_gemm_tn launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+// ---- mjb_traj_cost / mjb_traj_select: the checks; the kernels and their launches are in mjb_traj.hip ----
+static int check_traj_array(const mjbData* d, const char* fn, const char* what, const void* ptr, bool may_be_null, long nstep, long B, long n,
+                            long ss, long es, size_t esize = 8) {
+  const std::string pre = std::string(fn) + ": " + what;
+  if (ss < 0 || es < 0) return fail(MJB_ERR_ARG, pre + ": strides must be >= 0");
+  if (!ptr) return may_be_null ? MJB_OK : fail(MJB_ERR_ARG, pre + " is NULL");
+  __int128 hi;
+  if (!traj_highest_element(nstep, B, n, ss, es, hi)) return fail(MJB_ERR_ARG, pre + ": bad extent");
+  if (hi + 1 > ((__int128)1 << 60)) return fail(MJB_ERR_ARG, pre + ": the extent (T, batch, strides) lies beyond its allocation");
+  const int why = device_extent(d, ptr, (size_t)(hi + 1) * esize);
+  static const char* const msg[4] = {"", " is not device-accessible memory of this data object's device", ": no allocation found behind it",
+                                     ": the extent (T, batch, strides) lies beyond its allocation"};
+  return why ? fail(MJB_ERR_ARG, pre + msg[why]) : MJB_OK;
+}
+
+int mjb_traj_cost(mjbData* d, const mjbTrajCost* p) {
+  static const char* fn = "mjb_traj_cost";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_traj_cost: NULL argument");
+  const HostModel& h = d->model->h;
+  const long T = p->T, B = p->batch, nq = h.nq, nv = h.nv, nu = h.nu, nx = 2 * nv;
+  static const char* const msg[7] = {"", ": T must be >= 1", ": batch must be >= 1", ": nv must lie in [1, 64]", ": nu must lie in [1, 64]",
+                                     ": nq must lie in [nv, 2 nv]", ": (T + 1) * batch * 2 nv is too large"};
+  if (const int why = traj_cost_size_error(T, B, nq, nv, nu)) return fail(MJB_ERR_ARG, std::string(fn) + msg[why]);
+  const mjbStridedIn* st[4] = {&p->qpos0, &p->qvel0, &p->qpos, &p->qvel};
+  for (const mjbStridedIn* s : st)
+    if ((s->dtype != MJB_F32 && s->dtype != MJB_F64) || s->dtype != p->qpos0.dtype)
+      return fail(MJB_ERR_ARG, "mjb_traj_cost: qpos0, qvel0, qpos, qvel must share one dtype, MJB_F32 or MJB_F64");
+  if (p->ctrl.dtype != MJB_F32 && p->ctrl.dtype != MJB_F64) return fail(MJB_ERR_ARG, "mjb_traj_cost: ctrl dtype must be MJB_F32 or MJB_F64");
+  HIPCHK(hipSetDevice(d->device));
+  const size_t ss = p->qpos0.dtype == MJB_F32 ? 4 : 8, su = p->ctrl.dtype == MJB_F32 ? 4 : 8;
+  int rc;
+  if ((rc = check_traj_array(d, fn, "qpos0", p->qpos0.ptr, false, 1, B, nq, 0, p->qpos0.env_stride, ss)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "qvel0", p->qvel0.ptr, false, 1, B, nv, 0, p->qvel0.env_stride, ss)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "qpos", p->qpos.ptr, false, T, B, nq, p->qpos.step_stride, p->qpos.env_stride, ss)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "qvel", p->qvel.ptr, false, T, B, nv, p->qvel.step_stride, p->qvel.env_stride, ss)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "ctrl", p->ctrl.ptr, false, T, B, nu, p->ctrl.step_stride, p->ctrl.env_stride, su)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "qref", p->qref.ptr, false, T + 1, B, nq, p->qref.step_stride, p->qref.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "vref", p->vref.ptr, true, T + 1, B, nv, p->vref.step_stride, p->vref.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "uref", p->uref.ptr, true, T, B, nu, p->uref.step_stride, p->uref.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "Q", p->Q.ptr, false, T, B, nx * nx, p->Q.step_stride, p->Q.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "R", p->R.ptr, false, T, B, nu * nu, p->R.step_stride, p->R.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "Qf", p->Qf.ptr, false, 1, B, nx * nx, 0, p->Qf.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "cost", p->cost, false, 1, B, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "cost_t", p->cost_t, false, 1, B, T + 1, 0, T + 1)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "lx", p->lx, true, T, B, nx, B * nx, nx)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "lu", p->lu, true, T, B, nu, B * nu, nu)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "VxT", p->VxT, true, 1, B, nx, 0, nx)) != MJB_OK) return rc;
+  TrajCostArgs a;
+  a.T = p->T; a.B = p->batch; a.nq = h.nq; a.nv = h.nv; a.nu = h.nu; a.njnt = h.njnt;
+  a.state_f32 = p->qpos0.dtype == MJB_F32; a.ctrl_f32 = p->ctrl.dtype == MJB_F32;
+  auto in = [](const mjbStridedIn& s, bool per_env) { TrajIn r; r.p = s.ptr; r.ss = per_env ? 0 : s.step_stride; r.es = s.env_stride; return r; };
+  auto ref = [](const mjbStrided& s, bool per_env) { TrajRef r; r.p = s.ptr; r.ss = per_env ? 0 : s.step_stride; r.es = s.env_stride; return r; };
+  a.qpos0 = in(p->qpos0, true); a.qvel0 = in(p->qvel0, true); a.qpos = in(p->qpos, false); a.qvel = in(p->qvel, false); a.ctrl = in(p->ctrl, false);
+  a.qref = ref(p->qref, false); a.vref = ref(p->vref, false); a.uref = ref(p->uref, false);
+  a.Q = ref(p->Q, false); a.R = ref(p->R, false); a.Qf = ref(p->Qf, true);
+  a.jnt_type = d->md.jnt_type; a.jnt_qposadr = d->md.jnt_qposadr; a.jnt_dofadr = d->md.jnt_dofadr;
+  a.cost = p->cost; a.cost_t = p->cost_t; a.lx = p->lx; a.lu = p->lu; a.VxT = p->VxT;
+  const hipError_t e = traj_launch_cost(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_traj_cost launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+int mjb_traj_select(mjbData* d, const mjbTrajSelect* p) {
+  static const char* fn = "mjb_traj_select";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_traj_select: NULL argument");
+  static const char* const msg[7] = {"", ": nprob must lie in [1, 2^30]", ": ncand must lie in [1, 2^20]", ": T, nu must be >= 1 and T * nu <= 2^22",
+                                     ": mode must be MJB_SELECT_ARGMIN or MJB_SELECT_SOFTMIN", ": temperature must be finite and > 0",
+                                     ": nprob * ncand * T * nu is too large"};
+  if (const int why = traj_select_size_error(p->nprob, p->ncand, p->T, p->nu, p->mode, p->temperature)) return fail(MJB_ERR_ARG, std::string(fn) + msg[why]);
+  if ((p->cand_dtype != MJB_F32 && p->cand_dtype != MJB_F64) || (p->out_dtype != MJB_F32 && p->out_dtype != MJB_F64))
+    return fail(MJB_ERR_ARG, "mjb_traj_select: cand_dtype and out_dtype must be MJB_F32 or MJB_F64");
+  HIPCHK(hipSetDevice(d->device));
+  const long G = p->nprob, n = p->ncand, M = (long)p->T * p->nu;
+  int rc;
+  if ((rc = check_traj_array(d, fn, "cost", p->cost, false, 1, G, n, 0, n)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "cand", p->cand, false, 1, G, n * M, 0, n * M, p->cand_dtype == MJB_F32 ? 4 : 8)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "u_out", p->u_out, false, 1, G, M, 0, M, p->out_dtype == MJB_F32 ? 4 : 8)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "best", p->best, true, 1, G, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "best_cost", p->best_cost, true, 1, G, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "weights", p->weights, true, 1, G, n, 0, n)) != MJB_OK) return rc;
+  TrajSelectArgs a;
+  a.nprob = p->nprob; a.T = p->T; a.nu = p->nu; a.mode = p->mode; a.cand_f32 = p->cand_dtype == MJB_F32; a.out_f32 = p->out_dtype == MJB_F32;
+  a.ncand = p->ncand; a.temperature = p->temperature;
+  a.cost = p->cost; a.cand = p->cand; a.u_out = p->u_out; a.best = p->best; a.best_cost = p->best_cost; a.weights = p->weights;
+  const hipError_t e = traj_launch_select(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_traj_select launch: ") + hipGetErrorString(e));
   return MJB_OK;
 }
 

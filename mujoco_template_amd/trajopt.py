@@ -1,11 +1,16 @@
 """Trajectory optimisation on the GPU: the backward pass of a batched time-varying LQR / iLQR and the candidate controls of its line
-search, as one kernel launch each (``mjb_lqr_backward`` / ``mjb_lqr_candidates``, float64).
+search, as one kernel launch each (``mjb_lqr_backward`` / ``mjb_lqr_candidates``, float64), the quadratic trajectory cost with its
+first-order expansion (``mjb_traj_cost``) and the choice or softmin update over candidates (``mjb_traj_select``).
 
 With ``rollout`` and ``linearize_rollout`` these are the phases of an iLQR iteration, none of which leaves the GPU::
 
     state, _, A, B = linearize_rollout(model, data, u, initial_state=x0)       # A [B, T, nx, nx], B [B, T, nx, nu]
-    sol = lqr_backward(data, A, B, lx=lx, lu=lu, lxx=Q, luu=R, VxT=VxT, VxxT=Qf, mu=1e-6)
+    c = trajectory_cost(data, state, u, initial_state=x0, Q=Q, R=R, Qf=Qf, x_ref=x_ref)       # cost [B], lx, lu, VxT
+    sol = lqr_backward(data, A, B, lx=c.lx, lu=c.lu, lxx=Q, luu=R, VxT=c.VxT, VxxT=Qf, mu=1e-6)
     cand = lqr_candidates(data, A, B, sol.k, sol.K, u, alphas, lo=-u_max, hi=u_max)        # [B, nalpha, T, nu]
+    st, _ = rollout(model, search, cand[0], initial_state=x0)
+    cc = trajectory_cost(search, st, cand[0], initial_state=x0, Q=Q, R=R, Qf=Qf, x_ref=x_ref, gradients=False)
+    select_candidates(data, cc.cost[None], cand, out=u)                        # u <- the best candidate, no host read
 
 The reference designs its controllers from one ``(A, B)`` with ``scipy.linalg.solve_discrete_are``; with ``lx = lu = 0`` the backward
 pass is the finite-horizon, time-varying form of that recursion and ``K[:, t]`` the LQR gain of step ``t``.
@@ -37,16 +42,18 @@ def _sim(data):
     return getattr(data, "sim", data)
 
 
-def _strided(fn, name, x, trail, B, T, dev, time_major, optional=False):
-    """(address, step stride, env stride, tensor kept alive) of one input: full ``[B, T, *trail]`` / ``[T, B, *trail]`` or ``trail`` alone"""
+def _strided(fn, name, x, trail, B, T, dev, time_major, optional=False, dtypes=None):
+    """(address, step stride, env stride, tensor kept alive) of one input: full ``[B, T, *trail]`` / ``[T, B, *trail]`` or ``trail`` alone.
+    ``dtypes``: the element types accepted (float64 alone by default); the tensor returned tells which one it is."""
     import torch
 
     if x is None:
         if optional:
             return 0, 0, 0, None
         raise ConfigError(f"{fn}: {name} is required")
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != dev:
-        raise ConfigError(f"{fn}: {name} must be a float64 torch tensor on {dev}")
+    dtypes = (torch.float64,) if dtypes is None else tuple(dtypes)
+    if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or x.device != dev:
+        raise ConfigError(f"{fn}: {name} must be a {' or '.join(str(d).replace('torch.', '') for d in dtypes)} torch tensor on {dev}")
     trail = tuple(trail)
     lead = (T, B) if time_major else (B, T)
     if tuple(x.shape) == trail:
@@ -184,4 +191,161 @@ def lqr_candidates(data, A, B, k, K, u, alphas, *, dx0=None, lo=None, hi=None, d
     return cand
 
 
-__all__ = ["LqrBackwardResult", "lqr_backward", "lqr_candidates"]
+class TrajCostResult(NamedTuple):
+    cost: object     # [B] float64; +inf where the sum is not finite
+    cost_t: object   # [B, T + 1]
+    lx: object       # [B, T, nx] (a permuted view of the [T, B, nx] block lqr_backward reads in place), or None
+    lu: object       # [B, T, nu], or None
+    VxT: object      # [B, nx], or None
+
+
+class TrajSelectResult(NamedTuple):
+    u: object          # [nprob, T, nu] (``out`` itself when given)
+    best: object       # [nprob] int32: lowest index among the candidates of minimal finite cost, -1 when none is finite
+    best_cost: object  # [nprob] float64 (+inf when none is finite)
+    weights: object    # [nprob, ncand] float64 (softmin), or None
+
+
+def _dtype_code(t):
+    import torch
+
+    return 0 if t.dtype == torch.float32 else 1
+
+
+def trajectory_cost(data, state, control, *, initial_state, Q, R, Qf, x_ref=None, u_ref=None, gradients: bool = True) -> TrajCostResult:
+    """The quadratic cost of ``B`` trajectories of ``T + 1`` points and its first-order expansion, on the GPU (``mjb_traj_cost``)::
+
+        dx_t = [differentiatePos(qref_t -> qpos_t) ; qvel_t - vref_t]     du_t = u_t - uref_t          (2nv tangent space, float64)
+        cost = sum_{t<T} (dx_t' Q_t dx_t + du_t' R_t du_t) / 2 + dx_T' Qf dx_T / 2
+        lx[:, t] = Q_t dx_t     lu[:, t] = R_t du_t     VxT = Qf dx_T
+
+    ``state [B, T, 1+nq+nv]`` as ``rollout`` / ``linearize_rollout`` return it (float32 or float64, read in place: row ``t`` is the
+    state after step ``t``, the time column is skipped), ``control [B, T, nu]`` or ``[T, nu]`` (float32 or float64),
+    ``initial_state [B, 1+nq+nv]`` or ``[1+nq+nv]`` (converted to ``state``'s dtype if it differs - the rounding the rollout applied
+    to it).  ``x_ref [nq+nv]`` or ``[B, T+1, nq+nv]`` float64 (``None``: the model's ``qpos0`` at zero velocity), ``u_ref [nu]`` or
+    ``[B, T, nu]`` (``None``: 0); ``Q [nx, nx]`` or ``[B, T, nx, nx]`` with ``nx = 2 nv``, ``R [nu, nu]`` or ``[B, T, nu, nu]``,
+    ``Qf [nx, nx]`` or ``[B, nx, nx]``, float64, taken as symmetric.  ``B`` is ``state``'s and need not be the data's batch; the model
+    (``nq, nv, nu``, the joint table) is the data's.  ``gradients=False`` leaves ``lx, lu, VxT`` out (a line search needs the cost only).
+
+    A trajectory whose cost is NaN or infinite gets ``cost = +inf``; the others are unaffected.  A trajectory's results are bitwise
+    the same at any position of any batch.  Enqueued on torch's current stream; nothing waits for the GPU."""
+    import torch
+
+    fn = "trajectory_cost"
+    sim = _sim(data)
+    dev = torch.device(f"cuda:{sim.device}")
+    m = sim.model.compiled
+    nq, nv, nu = int(m.nq), int(m.nv), int(m.nu)
+    nx, ns = 2 * nv, 1 + nq + nv
+    both = (torch.float32, torch.float64)
+    if not isinstance(state, torch.Tensor) or state.ndim != 3 or state.shape[2] != ns:
+        raise ConfigError(f"{fn}: state must be a [B, T, {ns}] tensor (time, qpos, qvel)")
+    nb, T = int(state.shape[0]), int(state.shape[1])
+    if nb < 1 or T < 1:
+        raise ConfigError(f"{fn}: state must hold at least one trajectory of one step")
+    arrays, keep = {}, []
+    p, ss, es, state = _strided(fn, "state", state, (ns,), nb, T, dev, False, dtypes=both)
+    size, code = state.element_size(), _dtype_code(state)
+    arrays["qpos"] = (p + size, ss, es, code); arrays["qvel"] = (p + size * (1 + nq), ss, es, code); keep.append(state)
+    if isinstance(control, torch.Tensor) and control.ndim == 2 and tuple(control.shape) == (T, nu):
+        control = control.unsqueeze(0).expand(nb, T, nu)
+    if not isinstance(control, torch.Tensor) or tuple(control.shape) != (nb, T, nu):
+        raise ConfigError(f"{fn}: control must be a tensor [{nb}, {T}, {nu}] or [{T}, {nu}]")
+    p, ss, es, control = _strided(fn, "control", control, (nu,), nb, T, dev, False, dtypes=both)
+    arrays["ctrl"] = (p, ss, es, _dtype_code(control)); keep.append(control)
+    x0 = initial_state
+    if not isinstance(x0, torch.Tensor) or x0.dtype not in both or x0.device != dev or tuple(x0.shape) not in ((ns,), (nb, ns)):
+        raise ConfigError(f"{fn}: initial_state must be a float32 or float64 tensor [{nb}, {ns}] or [{ns}] on {dev}")
+    if x0.dtype != state.dtype:
+        x0 = x0.to(state.dtype)
+    if x0.stride(-1) != 1:
+        x0 = x0.contiguous()
+    es0 = x0.stride(0) if x0.ndim == 2 else 0
+    arrays["qpos0"] = (x0.data_ptr() + size, 0, es0, code); arrays["qvel0"] = (x0.data_ptr() + size * (1 + nq), 0, es0, code); keep.append(x0)
+    if x_ref is None:
+        x_ref = sim.__dict__.get("_traj_x_ref0")                 # the model's qpos0 at rest, uploaded once per data object
+        if x_ref is None or x_ref.device != dev:
+            import numpy as np
+
+            x_ref = torch.as_tensor(np.concatenate([np.asarray(m.qpos0, dtype=np.float64).reshape(-1), np.zeros(nv)])).to(dev)
+            sim.__dict__["_traj_x_ref0"] = x_ref
+    if not isinstance(x_ref, torch.Tensor) or x_ref.dtype != torch.float64 or x_ref.device != dev or \
+            tuple(x_ref.shape) not in ((nq + nv,), (nb, T + 1, nq + nv)):
+        raise ConfigError(f"{fn}: x_ref must be a float64 tensor [{nq + nv}] or [{nb}, {T + 1}, {nq + nv}] on {dev}")
+    if x_ref.stride(-1) != 1:
+        x_ref = x_ref.contiguous()
+    rs, re = (x_ref.stride(1), x_ref.stride(0)) if x_ref.ndim == 3 else (0, 0)
+    arrays["qref"] = (x_ref.data_ptr(), rs, re); arrays["vref"] = (x_ref.data_ptr() + 8 * nq, rs, re); keep.append(x_ref)
+    for name, x, trail, opt in (("uref", u_ref, (nu,), True), ("Q", Q, (nx, nx), False), ("R", R, (nu, nu), False)):
+        p, ss, es, t = _strided(fn, "u_ref" if name == "uref" else name, x, trail, nb, T, dev, False, optional=opt)
+        arrays[name] = (p, ss, es); keep.append(t)
+    if not isinstance(Qf, torch.Tensor) or Qf.dtype != torch.float64 or Qf.device != dev or tuple(Qf.shape) not in ((nx, nx), (nb, nx, nx)):
+        raise ConfigError(f"{fn}: Qf must be a float64 tensor [{nb}, {nx}, {nx}] or [{nx}, {nx}] on {dev}")
+    if not (Qf if Qf.ndim == 2 else Qf[0]).is_contiguous():
+        Qf = Qf.contiguous()
+    arrays["Qf"] = (Qf.data_ptr(), 0, 0 if Qf.ndim == 2 else Qf.stride(0)); keep.append(Qf)
+    for name, v in arrays.items():
+        if v[1] < 0 or v[2] < 0:
+            raise ConfigError(f"{fn}: {name} has a negative stride")
+    opt = dict(dtype=torch.float64, device=dev)
+    cost, cost_t = torch.empty((nb,), **opt), torch.empty((nb, T + 1), **opt)
+    lx = lu = VxT = None
+    if gradients:
+        lx, lu, VxT = torch.empty((T, nb, nx), **opt), torch.empty((T, nb, nu), **opt), torch.empty((nb, nx), **opt)
+    sim.traj_cost({"T": T, "batch": nb}, arrays,
+                  {"cost": cost.data_ptr(), "cost_t": cost_t.data_ptr(), "lx": lx.data_ptr() if gradients else 0,
+                   "lu": lu.data_ptr() if gradients else 0, "VxT": VxT.data_ptr() if gradients else 0}, keep=keep)
+    if gradients:
+        lx, lu = lx.permute(1, 0, 2), lu.permute(1, 0, 2)
+    return TrajCostResult(cost, cost_t, lx, lu, VxT)
+
+
+def select_candidates(data, cost, cand, *, mode: str = "argmin", temperature=None, out=None, dtype=None) -> TrajSelectResult:
+    """Choose among, or blend, ``ncand`` candidate control sequences for each of ``nprob`` problems on the GPU (``mjb_traj_select``).
+    ``cost [nprob, ncand]`` float64, ``cand [nprob, ncand, T, nu]`` float32 or float64 (what ``lqr_candidates`` returns; for a
+    sampling planner the control tensor itself with a leading axis of 1).
+
+    ``mode="argmin"``: ``u[g] = cand[g, best[g]]`` with ``best`` the lowest index among the candidates of minimal finite cost.
+    ``mode="softmin"`` (the MPPI update): ``u[g] = sum_j w_j cand[g, j]`` with ``w_j = exp(-(c_j - c_min) / temperature)`` over the
+    finite costs (0 for the others), normalised; accumulated in float64 and rounded once; ``weights`` holds the ``w_j``.
+    A problem without any finite cost gets ``best = -1``, ``best_cost = +inf`` and its ``u`` is NOT written: pass the nominal controls
+    as ``out [nprob, T, nu]`` and they are updated in place or kept (without ``out`` the result starts as zeros).  ``dtype``: the
+    result's (``out``'s when given; ``cand``'s by default).  Enqueued on torch's current stream; nothing waits for the GPU."""
+    import torch
+
+    fn = "select_candidates"
+    sim = _sim(data)
+    dev = torch.device(f"cuda:{sim.device}")
+    both = (torch.float32, torch.float64)
+    if mode not in ("argmin", "softmin"):
+        raise ConfigError(f"{fn}: mode must be 'argmin' or 'softmin', got {mode!r}")
+    if mode == "softmin" and temperature is None:
+        raise ConfigError(f"{fn}: mode 'softmin' needs a temperature")
+    if not isinstance(cand, torch.Tensor) or cand.ndim != 4 or cand.dtype not in both or cand.device != dev:
+        raise ConfigError(f"{fn}: cand must be a float32 or float64 tensor [nprob, ncand, T, nu] on {dev}")
+    G, n, T, nu = (int(v) for v in cand.shape)
+    if not isinstance(cost, torch.Tensor) or cost.dtype != torch.float64 or cost.device != dev or tuple(cost.shape) != (G, n):
+        raise ConfigError(f"{fn}: cost must be a float64 tensor [{G}, {n}] on {dev}")
+    cost, cand = cost.contiguous(), cand.contiguous()
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype not in both or out.device != dev or tuple(out.shape) != (G, T, nu) or not out.is_contiguous():
+            raise ConfigError(f"{fn}: out must be a contiguous float32 or float64 tensor [{G}, {T}, {nu}] on {dev}")
+        if dtype is not None and dtype != out.dtype:
+            raise ConfigError(f"{fn}: dtype {dtype} differs from out's {out.dtype}")
+        u = out
+    else:
+        dtype = cand.dtype if dtype is None else dtype
+        if dtype not in both:
+            raise ConfigError(f"{fn}: dtype must be torch.float64 or torch.float32")
+        u = torch.zeros((G, T, nu), dtype=dtype, device=dev)
+    best = torch.empty((G,), dtype=torch.int32, device=dev)
+    best_cost = torch.empty((G,), dtype=torch.float64, device=dev)
+    weights = torch.empty((G, n), dtype=torch.float64, device=dev) if mode == "softmin" else None
+    sim.traj_select({"nprob": G, "ncand": n, "T": T, "nu": nu, "mode": int(mode == "softmin"), "cand_dtype": _dtype_code(cand),
+                     "out_dtype": _dtype_code(u), "temperature": 0.0 if temperature is None else float(temperature)},
+                    {"cost": cost.data_ptr(), "cand": cand.data_ptr(), "u_out": u.data_ptr(), "best": best.data_ptr(),
+                     "best_cost": best_cost.data_ptr(), "weights": weights.data_ptr() if weights is not None else 0}, keep=[cost, cand, u])
+    return TrajSelectResult(u, best, best_cost, weights)
+
+
+__all__ = ["LqrBackwardResult", "lqr_backward", "lqr_candidates", "TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]

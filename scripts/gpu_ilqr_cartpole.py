@@ -8,10 +8,15 @@ Each iteration (horizon T, one nominal control sequence):
              the candidate controls come from the closed loop run on the LINEARISED dynamics: dx' = A dx + B du,
              du = alpha k + K dx (``lqr_candidates``, one launch; with --backward torch a second torch loop); the true cost of each
              candidate is evaluated on the simulated states and the best one is kept.
+  cost       --cost kernel (the default with --backward kernel): the trajectory cost, its expansion lx / lu / VxT and the choice of the
+             step come from ``trajectory_cost`` and ``select_candidates``; the nominal controls are updated in place through ``out=``,
+             the per-iteration costs stay on the GPU and are read once at the end - apart from the synchronises that close the timed
+             phases, an iteration never waits for the GPU.  --cost torch: the einsum cost, ``xs @ Q`` / ``u @ R`` / ``Qf @ xs[T]`` and
+             a host ``argmin``, as before.
 The pole starts tilted by --tilt rad; the cost asks for the upright pole at the origin.  Prints one JSON line: cost per iteration,
 the tilt at the end of the final trajectory and the wall time of each phase (each closed by a device synchronise).
 
-    python scripts/gpu_ilqr_cartpole.py [--horizon 100] [--iters 15] [--alphas 16] [--tilt 0.3] [--backward kernel|torch] [--out FILE.json]
+    python scripts/gpu_ilqr_cartpole.py [--horizon 100] [--iters 15] [--alphas 16] [--tilt 0.3] [--backward kernel|torch] [--cost kernel|torch] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from mujoco_template_amd import linearize_rollout, lqr_backward, lqr_candidates, mj, rollout  # noqa: E402
+from mujoco_template_amd import linearize_rollout, lqr_backward, lqr_candidates, mj, rollout, select_candidates, trajectory_cost  # noqa: E402
 
 XML = os.path.join(ROOT, "models", "cartpole.xml")
 U_MAX = 4.0
@@ -39,8 +44,13 @@ def main():
     ap.add_argument("--alphas", type=int, default=16)
     ap.add_argument("--tilt", type=float, default=0.3)
     ap.add_argument("--backward", choices=("kernel", "torch"), default="kernel")
+    ap.add_argument("--cost", choices=("kernel", "torch"), default=None, help="default: kernel with --backward kernel, torch otherwise")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.cost is None:
+        args.cost = "kernel" if args.backward == "kernel" else "torch"
+    if args.cost == "kernel" and args.backward != "kernel":
+        raise SystemExit("--cost kernel feeds lqr_backward: it needs --backward kernel")
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: the rollouts and linearisations run on the MI355X")
     T, K = args.horizon, args.alphas
@@ -66,11 +76,31 @@ def main():
     u = torch.zeros((1, T, nu), dtype=f64, device=dev)
     costs, split = [], {"linearise": 0.0, "backward": 0.0, "forward": 0.0}
     reg = 1e-6
-    for _ in range(args.iters):
+    # --cost kernel: the script's cost has no state term at t = 0, so Q is passed per step with Q_0 = 0; the goal is the origin
+    x0_dev, x_goal = x0.to(dev), torch.zeros(nq + nv, dtype=f64, device=dev)
+    Qt = Q.expand(T, nx, nx).clone()
+    Qt[0] = 0
+    Qt1, QtK = Qt[None], Qt[None].expand(K, T, nx, nx)
+    cost_dev = torch.zeros(args.iters + 1, dtype=f64, device=dev)
+    for it in range(args.iters):
         t0 = time.perf_counter()
         state, _, A, Bm = linearize_rollout(model, nominal, u, initial_state=x0)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
+        if args.cost == "kernel":
+            c0 = trajectory_cost(nominal, state, u, initial_state=x0_dev, Q=Qt1, R=R, Qf=Qf, x_ref=x_goal)
+            cost_dev[it:it + 1].copy_(c0.cost)
+            sol = lqr_backward(nominal, A, Bm, lx=c0.lx, lu=c0.lu, lxx=Qt1, luu=R, VxT=c0.VxT, VxxT=Qf, mu=reg)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            cand = lqr_candidates(nominal, A, Bm, sol.k, sol.K, u, alphas, lo=-U_MAX, hi=U_MAX)
+            st, _ = rollout(model, search, cand[0], initial_state=x0)
+            cc = trajectory_cost(search, st, cand[0], initial_state=x0_dev, Q=QtK, R=R, Qf=Qf, x_ref=x_goal, gradients=False)
+            select_candidates(nominal, cc.cost[None], cand, out=u)             # u <- the best candidate (a NaN rollout costs +inf)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            split["linearise"] += t1 - t0; split["backward"] += t2 - t1; split["forward"] += t3 - t2
+            continue
         costs.append(float(cost(state, u)[0]))
         xs = torch.cat([x0[1:].to(dev)[None], state[0, :, 1:]])                # [T + 1, nx]: x_t before step t, x_T the last state
         if args.backward == "kernel":
@@ -110,8 +140,12 @@ def main():
         t3 = time.perf_counter()
         split["linearise"] += t1 - t0; split["backward"] += t2 - t1; split["forward"] += t3 - t2
     state, _ = rollout(model, nominal, u, initial_state=x0)
-    costs.append(float(cost(state, u)[0]))
-    res = {"backward": args.backward, "horizon": T, "iterations": args.iters, "alphas": K, "tilt0_rad": args.tilt, "cost_per_iteration": costs,
+    if args.cost == "kernel":
+        cost_dev[args.iters:].copy_(trajectory_cost(nominal, state, u, initial_state=x0_dev, Q=Qt1, R=R, Qf=Qf, x_ref=x_goal, gradients=False).cost)
+        costs = cost_dev.tolist()                                              # the one host read of the costs
+    else:
+        costs.append(float(cost(state, u)[0]))
+    res = {"backward": args.backward, "cost": args.cost, "horizon": T, "iterations": args.iters, "alphas": K, "tilt0_rad": args.tilt, "cost_per_iteration": costs,
            "final_tilt_rad": float(state[0, -1, 2]), "final_slider_m": float(state[0, -1, 1]),
            "wall_s": {k: v for k, v in split.items()}, "wall_share": {k: v / sum(split.values()) for k, v in split.items()}}
     print(json.dumps(res), flush=True)

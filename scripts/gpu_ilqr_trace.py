@@ -4,7 +4,8 @@ and the digest of that run's CSV files.
 The iteration is ``linearize_rollout`` -> cost expansion (torch) -> ``lqr_backward`` -> ``lqr_candidates`` -> ``rollout`` (one environment
 per step size) -> cost of every candidate and the choice of the best one (torch, on the device).  Two warm-up iterations run first;
 the traced one is separated from them and from the final read-back by a device synchronise and a pause of --gap seconds, so that
-the digest finds it as the last burst of kernels that holds a ``k_lqr_backward`` dispatch.
+the digest finds it as the last burst of kernels that holds a ``k_lqr_backward`` dispatch.  With ``--cost kernel`` the cost, its
+expansion and the choice come from ``trajectory_cost`` / ``select_candidates`` (the nominal controls updated in place) instead of torch.
 
     rocprofv3 --kernel-trace --memory-copy-trace --hip-runtime-trace -d DIR -o ilqr --output-format csv -- python scripts/gpu_ilqr_trace.py
     python scripts/gpu_ilqr_trace.py --digest DIR > profiles/lqr_ilqr_iteration_trace.log
@@ -26,7 +27,7 @@ U_MAX = 4.0
 def run(args):
     import torch
 
-    from mujoco_template_amd import linearize_rollout, lqr_backward, lqr_candidates, mj, rollout
+    from mujoco_template_amd import linearize_rollout, lqr_backward, lqr_candidates, mj, rollout, select_candidates, trajectory_cost
 
     T, K = args.horizon, args.alphas
     dev, f64 = torch.device("cuda"), torch.float64
@@ -63,6 +64,22 @@ def run(args):
         best = torch.argmin(torch.nan_to_num(c, nan=float("inf")))
         return cand.index_select(0, best[None]), c, sol.status
 
+    x_goal = torch.zeros(nq + nv, dtype=f64, device=dev)
+    lxxK = lxx.expand(K, T, nx, nx)
+
+    def iteration_kernel(u):
+        """The same iteration on trajectory_cost / select_candidates: u is updated in place."""
+        state, _, A, Bm = linearize_rollout(model, nominal, u, initial_state=x0)
+        c0 = trajectory_cost(nominal, state, u, initial_state=x0, Q=lxx, R=R, Qf=Qf, x_ref=x_goal)
+        sol = lqr_backward(nominal, A, Bm, lx=c0.lx, lu=c0.lu, lxx=lxx, luu=R, VxT=c0.VxT, VxxT=Qf, mu=mu)
+        cand = lqr_candidates(nominal, A, Bm, sol.k, sol.K, u, alphas, lo=lo, hi=hi)
+        st, _ = rollout(model, search, cand[0], initial_state=x0)
+        cc = trajectory_cost(search, st, cand[0], initial_state=x0, Q=lxxK, R=R, Qf=Qf, x_ref=x_goal, gradients=False)
+        select_candidates(nominal, cc.cost[None], cand, out=u)
+        return u, cc.cost, sol.status
+
+    if args.cost == "kernel":
+        iteration = iteration_kernel
     u = torch.zeros((1, T, nu), dtype=f64, device=dev)
     for _ in range(2):                                           # warm-up: allocations, kernel loading, the FD scratch
         u, c, status = iteration(u)
@@ -98,6 +115,8 @@ def digest(d, gap_s):
     win = with_lqr[-1]
     t0, t1 = int(win[0]["Start_Timestamp"]), max(int(r["End_Timestamp"]) for r in win)
     print("# rocprofv3 --kernel-trace --memory-copy-trace --hip-runtime-trace -- python scripts/gpu_ilqr_trace.py   (its own run, no counters)")
+    if any("k_traj_cost" in r["Kernel_Name"] for r in win):
+        print("# --cost kernel: the cost, its expansion and the choice are trajectory_cost / select_candidates (k_traj_*)")
     print("# cart-pole iLQR, T = 100, 16 step sizes, float64: ONE iteration (linearize_rollout -> lqr_backward -> lqr_candidates -> rollout -> choice of")
     print("# the best candidate), enqueued back to back after two warm-up iterations; window = first to last kernel of that iteration")
     print()
@@ -105,7 +124,7 @@ def digest(d, gap_s):
     print(f"window: {len(win)} dispatches, {(t1 - t0) / 1e3:.1f} us from the first kernel's start to the last kernel's end")
     print()
     print("dispatches in the window, in order (torch's own kernels folded into one line per run of them):")
-    ours, run_n, run_t = ("mjb_k", "k_fd", "k_lqr", "k_obs", "k_step", "k_prm", "k_reset"), 0, 0.0
+    ours, run_n, run_t = ("mjb_k", "k_fd", "k_lqr", "k_traj", "k_obs", "k_step", "k_prm", "k_reset"), 0, 0.0
 
     def flush():
         nonlocal run_n, run_t
@@ -165,6 +184,7 @@ def main():
     ap.add_argument("--horizon", type=int, default=100)
     ap.add_argument("--alphas", type=int, default=16)
     ap.add_argument("--gap", type=float, default=0.5)
+    ap.add_argument("--cost", choices=("kernel", "torch"), default="torch")
     ap.add_argument("--digest", default=None, metavar="DIR")
     args = ap.parse_args()
     if args.digest:
