@@ -342,6 +342,34 @@ typedef struct mjbLqrBackward {
 } mjbLqrBackward;
 int mjb_lqr_backward(mjbData* d, const mjbLqrBackward* p);
 
+/* Control-limited form of mjb_lqr_backward (control-limited DDP: Tassa, Mansard, Todorov, ICRA 2014) for controls that stay inside a
+ * box lo <= u <= hi - the reference clips its LQR law to the model's ctrlrange (examples/humanoid/controllers/lqr.py:147-170), and a
+ * backward pass that does not know the limits returns gains that push a saturated actuator further into its bound.
+ * `base` is read exactly as mjb_lqr_backward reads it (Qx, Qu, Qxx, Quu, Qux are formed the same way, mu included); u [nu] per (t, e)
+ * are the nominal controls; lo / hi [nu] (NULL, or +-inf entries: unbounded on that side; lo <= hi is the caller's duty).  Per step,
+ * with lob = lo - u_t, hib = hi - u_t:
+ *   1. the QP  min x' Quu x / 2 + Qu' x,  lob <= x <= hib  by projected Newton from x = clip(0, lob, hib): g = Qu + Quu x, clamped set
+ *      c = (x == lob & g > 0) | (x == hib & g < 0), Newton target x*_f = -Quu_ff^-1 (Qu_f + Quu_fc x_c), x*_c = x_c (a point, not an
+ *      increment).  Inside the box it is taken whole, and the QP ends when the clamped set at x* equals c (tolerance-free, finite);
+ *      otherwise an Armijo search (ratio 0.1, factor 0.6) on clip(x + s (x* - x)).  No free control: done.  At most 64 iterations and
+ *      64 search trials (compile-time constants: the kernel ends in bounded time on any input); a cap or a failed search keeps the
+ *      last iterate;
+ *   2. the polish, one solve on the final set: [K | k]_f = -Quu_ff^-1 [Qux_f | Qu_f + Quu_fc x_c], K_c = 0, k_c = the bound itself
+ *      (lob or hib as computed), then k = clip(k, lob, hib) - accuracy does not depend on a QP tolerance, and with an empty set the
+ *      step is bitwise that of mjb_lqr_backward;
+ *   3. the value update and dV of mjb_lqr_backward with this k, K and the full Quu.
+ * status[e]: 1 + t for a pivot that is <= 0 or not finite in any factorisation of step t (as mjb_lqr_backward: zeros, the other
+ * trajectories untouched), else -(1 + t) for the highest step whose QP hit a cap or whose search failed (results finite and inside
+ * the box), else 0.  clamped [T, batch] int32: bit a set when control a is clamped at that step (0 for steps not solved);
+ * qp_iters [batch] int32: the largest iteration count of any step.  Checks, launch and stream as mjb_lqr_backward. */
+typedef struct mjbLqrBackwardBox {
+  mjbLqrBackward base;
+  mjbStrided u;
+  const double *lo, *hi;
+  int *clamped, *qp_iters;
+} mjbLqrBackwardBox;
+int mjb_lqr_backward_box(mjbData* d, const mjbLqrBackwardBox* p);
+
 /* For every trajectory e and step size alphas[j], from dx = dx0[e] (ptr NULL = 0; step_stride ignored):
  *   c_t = clamp(u_t + alphas[j] k_t + K_t dx, lo, hi),  dx = A_t dx + B_t (c_t - u_t)     for t = 0 .. T-1
  * cand [batch, nalpha, T, nu] dense, float64 or (out_f32 != 0) float32 = the float64 value rounded once - what mjb_rollout_ctrl of a

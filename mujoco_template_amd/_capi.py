@@ -49,6 +49,11 @@ class LqrBackwardStruct(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("k", "K", "dV", "V0x", "V0xx", "status")]
 
 
+class LqrBackwardBoxStruct(ctypes.Structure):
+    """``mjbLqrBackwardBox`` (include/mjbatch.h)."""
+    _fields_ = [("base", LqrBackwardStruct), ("u", Strided)] + [(n, ctypes.c_void_p) for n in ("lo", "hi", "clamped", "qp_iters")]
+
+
 class LqrCandidatesStruct(ctypes.Structure):
     """``mjbLqrCandidates`` (include/mjbatch.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("T", "batch", "nx", "nu", "nalpha", "out_f32")] + \
@@ -147,6 +152,8 @@ def load_library() -> ctypes.CDLL:
     L.mjb_fd_points_slabs.restype = ci
     L.mjb_lqr_backward.argtypes = [vp, ctypes.POINTER(LqrBackwardStruct)]
     L.mjb_lqr_backward.restype = ci
+    L.mjb_lqr_backward_box.argtypes = [vp, ctypes.POINTER(LqrBackwardBoxStruct)]
+    L.mjb_lqr_backward_box.restype = ci
     L.mjb_lqr_candidates.argtypes = [vp, ctypes.POINTER(LqrCandidatesStruct)]
     L.mjb_lqr_candidates.restype = ci
     L.mjb_lqr_gemm_tn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
@@ -1028,6 +1035,18 @@ class BatchSim:
         need none: they are allocated on the stream the kernel runs on).  Enqueued on torch's current
         stream, nothing waits for the GPU.  ``trajopt.lqr_backward`` is the checked tensor interface on top of it."""
         self._lqr_call(load_library().mjb_lqr_backward, LqrBackwardStruct(), sizes, arrays, pointers, keep)
+
+    def lqr_backward_box(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_lqr_backward_box`` on raw device addresses (see ``lqr_backward``): ``arrays`` also holds ``u``, ``pointers`` also
+        ``lo``, ``hi`` (0 = unbounded), ``clamped`` and ``qp_iters``."""
+        struct, own = LqrBackwardBoxStruct(), ("u", "lo", "hi", "clamped", "qp_iters")
+        for k, v in sizes.items():
+            setattr(struct.base, k, int(v))
+        for k, v in arrays.items():
+            setattr(struct if k in own else struct.base, k, Strided(v[0] or None, int(v[1]), int(v[2])))
+        for k, ptr in pointers.items():
+            setattr(struct if k in own else struct.base, k, ptr or None)
+        self._lqr_call(load_library().mjb_lqr_backward_box, struct, {}, {}, {}, keep)
 
     def lqr_candidates(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
         """``mjb_lqr_candidates`` on raw device addresses (see ``lqr_backward``)."""

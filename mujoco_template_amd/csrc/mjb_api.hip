@@ -1626,7 +1626,7 @@ int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step
 
 int mjb_fd_points_slabs(const mjbData* d) { return d ? d->last_fd_slabs : -1; }
 
-// ---- mjb_lqr_backward / mjb_lqr_candidates: the checks; the kernels and their launches are in mjb_lqr.hip ----
+// ---- mjb_lqr_backward / mjb_lqr_backward_box / mjb_lqr_candidates: the checks; the kernels and their launches are in mjb_lqr.hip ----
 // One strided float64 (or esize-byte) array of `n` elements per (t, e), T x B blocks: pointer, strides, extent
 static int check_lqr_array(const mjbData* d, const char* fn, const char* what, const void* ptr, bool may_be_null, long T, long B, long n,
                            long ss, long es, size_t esize = 8) {
@@ -1677,6 +1677,43 @@ int mjb_lqr_backward(mjbData* d, const mjbLqrBackward* p) {
   a.k = p->k; a.K = p->K; a.dV = p->dV; a.V0x = p->V0x; a.V0xx = p->V0xx; a.status = p->status;
   const hipError_t e = lqr_launch_backward(a, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_backward launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+int mjb_lqr_backward_box(mjbData* d, const mjbLqrBackwardBox* q) {
+  static const char* fn = "mjb_lqr_backward_box";
+  if (!d || !q) return fail(MJB_ERR_ARG, "mjb_lqr_backward_box: NULL argument");
+  const mjbLqrBackward* p = &q->base;
+  int rc;
+  if ((rc = check_lqr_sizes(fn, p->T, p->batch, p->nx, p->nu)) != MJB_OK) return rc;
+  HIPCHK(hipSetDevice(d->device));
+  const long T = p->T, B = p->batch, nx = p->nx, nu = p->nu;
+  const struct { const char* what; const mjbStrided* s; long n; bool opt; } in[] = {
+      {"A", &p->A, nx * nx, false}, {"B", &p->B, nx * nu, false}, {"lx", &p->lx, nx, false}, {"lu", &p->lu, nu, false},
+      {"lxx", &p->lxx, nx * nx, false}, {"luu", &p->luu, nu * nu, false}, {"lux", &p->lux, nu * nx, true}, {"u", &q->u, nu, false}};
+  for (const auto& a : in)
+    if ((rc = check_lqr_array(d, fn, a.what, a.s->ptr, a.opt, T, B, a.n, a.s->step_stride, a.s->env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "VxT", p->VxT.ptr, false, 1, B, nx, 0, p->VxT.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "VxxT", p->VxxT.ptr, false, 1, B, nx * nx, 0, p->VxxT.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "mu", p->mu.ptr, false, 1, B, 1, 0, p->mu.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "lo", q->lo, true, 1, 1, nu, 0, 0)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "hi", q->hi, true, 1, 1, nu, 0, 0)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "k", p->k, false, T, B, nu, B * nu, nu)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "K", p->K, false, T, B, nu * nx, B * nu * nx, nu * nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "dV", p->dV, false, 1, B, 2, 0, 2)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "V0x", p->V0x, true, 1, B, nx, 0, nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "V0xx", p->V0xx, true, 1, B, nx * nx, 0, nx * nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "status", p->status, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "clamped", q->clamped, false, T, B, 1, B, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "qp_iters", q->qp_iters, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  LqrBoxArgs a;
+  a.b.T = p->T; a.b.B = p->batch; a.b.nx = p->nx; a.b.nu = p->nu;
+  a.b.A = lqr_arr(p->A); a.b.Bm = lqr_arr(p->B); a.b.lx = lqr_arr(p->lx); a.b.lu = lqr_arr(p->lu); a.b.lxx = lqr_arr(p->lxx); a.b.luu = lqr_arr(p->luu);
+  a.b.lux = lqr_arr(p->lux); a.b.VxT = lqr_arr(p->VxT); a.b.VxxT = lqr_arr(p->VxxT); a.b.mu = lqr_arr(p->mu);
+  a.b.k = p->k; a.b.K = p->K; a.b.dV = p->dV; a.b.V0x = p->V0x; a.b.V0xx = p->V0xx; a.b.status = p->status;
+  a.u = lqr_arr(q->u); a.lo = q->lo; a.hi = q->hi; a.clamped = q->clamped; a.qp_iters = q->qp_iters;
+  const hipError_t e = lqr_launch_backward_box(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_backward_box launch: ") + hipGetErrorString(e));
   return MJB_OK;
 }
 

@@ -1,4 +1,4 @@
-// The kernels of mjb_lqr_backward / mjb_lqr_candidates (mjb_lqr.hpp) and their launches.  One workgroup per trajectory.
+// The kernels of mjb_lqr_backward / mjb_lqr_backward_box / mjb_lqr_candidates (mjb_lqr.hpp) and their launches.  One workgroup per trajectory.
 #include "mjb_lqr.hpp"
 
 namespace mjb {
@@ -7,6 +7,9 @@ extern __shared__ double lqr_lds[];
 
 template <int NW, int MU> __global__ __launch_bounds__(64 * NW) void k_lqr_backward(LqrBackwardArgs p) {
   lqr_backward_env<NW, MU>(p, (int)blockIdx.x, (int)threadIdx.x, lqr_lds);
+}
+template <int NW, int MU> __global__ __launch_bounds__(64 * NW) void k_lqr_backward_box(LqrBoxArgs p) {
+  lqr_backward_box_env<NW, MU>(p, (int)blockIdx.x, (int)threadIdx.x, lqr_lds);
 }
 __global__ __launch_bounds__(256) void k_lqr_candidates(LqrCandArgs p) {
   lqr_candidates_env<256>(p, (int)blockIdx.x, (int)threadIdx.x, lqr_lds);
@@ -42,6 +45,24 @@ hipError_t lqr_launch_backward(const LqrBackwardArgs& p, hipStream_t stream) {
   } else {
     if ((e = lqr_lds_limit<k_lqr_backward<4, kLqrMaxNu>>(bytes)) != hipSuccess) return e;
     hipLaunchKernelGGL((k_lqr_backward<4, kLqrMaxNu>), dim3((unsigned)p.B), dim3(256), bytes, stream, p);
+  }
+  return hipGetLastError();
+}
+
+hipError_t lqr_launch_backward_box(const LqrBoxArgs& p, hipStream_t stream) {      // the dispatch of lqr_launch_backward
+  const int nx = p.b.nx, nu = p.b.nu;
+  const size_t bytes = (size_t)lqr_box_layout(nx, nu).total * sizeof(double);
+  const unsigned B = (unsigned)p.b.B;
+  hipError_t e;
+  if (lqr_waves(nx) == 1 && nu <= 8) {
+    if ((e = lqr_lds_limit<k_lqr_backward_box<1, 8>>(bytes)) != hipSuccess) return e;
+    hipLaunchKernelGGL((k_lqr_backward_box<1, 8>), dim3(B), dim3(64), bytes, stream, p);
+  } else if (lqr_waves(nx) == 1) {
+    if ((e = lqr_lds_limit<k_lqr_backward_box<1, kLqrMaxNu>>(bytes)) != hipSuccess) return e;
+    hipLaunchKernelGGL((k_lqr_backward_box<1, kLqrMaxNu>), dim3(B), dim3(64), bytes, stream, p);
+  } else {
+    if ((e = lqr_lds_limit<k_lqr_backward_box<4, kLqrMaxNu>>(bytes)) != hipSuccess) return e;
+    hipLaunchKernelGGL((k_lqr_backward_box<4, kLqrMaxNu>), dim3(B), dim3(256), bytes, stream, p);
   }
   return hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// mjb_lqr.hpp — the backward pass of a batched time-varying LQR / iLQR (mjb_lqr_backward) and the line search's candidate controls
-// (mjb_lqr_candidates) as workgroup-cooperative float64 device code.
+// mjb_lqr.hpp — the backward pass of a batched time-varying LQR / iLQR (mjb_lqr_backward), its control-limited form
+// (mjb_lqr_backward_box) and the line search's candidate controls (mjb_lqr_candidates) as workgroup-cooperative float64 device code.
 //
 // One workgroup advances one trajectory: T steps in series, Vxx and every per-step temporary resident in LDS, the products on
 // v_mfma_f64_16x16x4_f64 tiles (lqr_gemm_tn), the next step's (A, B) blocks in flight in registers while the current step computes.
@@ -35,6 +35,15 @@ struct LqrBackwardArgs {
   LqrStrided VxT, VxxT, mu;                         // terminal values / regularisation: env stride only
   double *k, *K, *dV, *V0x, *V0xx;                  // k [T, B, nu], K [T, B, nu, nx], dV [B, 2]; V0x [B, nx], V0xx [B, nx, nx] may be null
   int* status;                                      // [B]
+};
+
+// mjb_lqr_backward_box: the arguments above plus the nominal controls u [nu] per (t, e), the box lo / hi [nu] (null = unbounded on
+// that side) and two more outputs, clamped [T, B] (bit a = control a clamped at that step) and qp_iters [B]
+struct LqrBoxArgs {
+  LqrBackwardArgs b;
+  LqrStrided u;
+  const double *lo, *hi;
+  int *clamped, *qp_iters;
 };
 
 struct LqrCandArgs {
@@ -73,6 +82,26 @@ MJB_LQR_HD LqrLay lqr_layout(int nx, int nu) {
   l.S = o; o += nu * nx;
   l.total = o > end1 ? o : end1;
   return l;
+}
+// Control-limited backward pass: the layout above, and after S in the solve half of the union the QP's vectors - the iterate x, the
+// Newton target xs, the gradient g, the box lob / hib of the step, the clamped and the inside-the-box flags (one word per control), and
+// one flag per search trial.
+static const int kLqrQpIters = 64, kLqrQpTrials = 64;            // the caps: the kernel ends in bounded time on any input
+struct LqrBoxLay { LqrLay l; int x, xs, g, lob, hib, cf, fe, pass, total; };
+MJB_LQR_HD LqrBoxLay lqr_box_layout(int nx, int nu) {
+  LqrBoxLay b;
+  b.l = lqr_layout(nx, nu);
+  int o = b.l.S + nu * nx;
+  b.x = o; o += nu;
+  b.xs = o; o += nu;
+  b.g = o; o += nu;
+  b.lob = o; o += nu;
+  b.hib = o; o += nu;
+  b.cf = o; o += nu;
+  b.fe = o; o += nu;
+  b.pass = o; o += kLqrQpTrials;
+  b.total = o > b.l.total ? o : b.l.total;
+  return b;
 }
 // Candidates: the step's A (row stride nx | 1: the mat-vec reads a column of lanes down the rows), B, K (row stride nx | 1), k, u and
 // per step size the deviation dx (two copies: read one, write the other) and du = c - u.
@@ -217,177 +246,387 @@ MJB_LQR_DEV void lqr_gemm_probe(int M, int N, int K, const double* a, const doub
                   [&](int row, int col, double v) { c[row * N + col] = v; });
 }
 
+// ---- the pieces of one step, shared by lqr_backward_env and lqr_backward_box_env ----------------------------------------------
+struct LqrLds { double *Vxx, *Vx, *Qux, *Quu, *Qx, *Qu, *wq, *A, *B, *VA, *VB, *Qw, *L, *R, *S; };
+MJB_LQR_DEV LqrLds lqr_lds_pointers(double* w, const LqrLay& l) {
+  LqrLds m;
+  m.Vxx = w + l.Vxx; m.Vx = w + l.Vx; m.Qux = w + l.Qux; m.Quu = w + l.Quu; m.Qx = w + l.Qx; m.Qu = w + l.Qu; m.wq = w + l.wq;
+  m.A = w + l.A; m.B = w + l.B; m.VA = w + l.VA; m.VB = w + l.VB; m.Qw = w + l.Qw; m.L = w + l.L; m.R = w + l.R; m.S = w + l.S;
+  return m;
+}
+
+// Vxx = VxxT, Vx = VxT and the last step's (A, B) into LDS
+template <int NT>
+MJB_LQR_DEV void lqr_load_terminal(const LqrBackwardArgs& p, int e, const LqrLds& m, int tid) {
+  const int nx = p.nx, nu = p.nu;
+  const double* Ag = p.A.p + (long)e * p.A.es;
+  const double* Bg = p.Bm.p + (long)e * p.Bm.es;
+  for (int i = tid; i < nx * nx; i += NT) m.Vxx[i] = p.VxxT.p[(long)e * p.VxxT.es + i];
+  for (int i = tid; i < nx; i += NT) m.Vx[i] = p.VxT.p[(long)e * p.VxT.es + i];
+  for (int i = tid; i < nx * nx; i += NT) m.A[i] = Ag[(long)(p.T - 1) * p.A.ss + i];
+  for (int i = tid; i < nx * nu; i += NT) m.B[i] = Bg[(long)(p.T - 1) * p.Bm.ss + i];
+  lqr_sync();
+}
+
+// the blocks of step t - 1 into registers (zeros at t = 0): issued at the start of step t, written to LDS at its end (lqr_step_end)
+template <int NT, int PA, int PB>
+MJB_LQR_DEV void lqr_prefetch(const LqrBackwardArgs& p, int t, int e, int tid, double (&ra)[PA], double (&rb)[PB]) {
+  const int nx = p.nx, nu = p.nu;
+  const double* Ag = p.A.p + (long)e * p.A.es;
+  const double* Bg = p.Bm.p + (long)e * p.Bm.es;
+#pragma unroll
+  for (int n = 0; n < PA; n++) { const int i = tid + n * NT; ra[n] = (t > 0 && i < nx * nx) ? Ag[(long)(t - 1) * p.A.ss + i] : 0.0; }
+#pragma unroll
+  for (int n = 0; n < PB; n++) { const int i = tid + n * NT; rb[n] = (t > 0 && i < nx * nu) ? Bg[(long)(t - 1) * p.Bm.ss + i] : 0.0; }
+}
+
+// VA = Vxx A, VB = Vxx B, then Qxx = lxx + A^T VA (into Vxx, which nothing reads any more), Qux = lux + B^T VA,
+// Quu = luu + B^T VB + mu I, Qx = lx + A^T Vx, Qu = lu + B^T Vx
+template <int NW>
+MJB_LQR_DEV void lqr_step_products(const LqrBackwardArgs& p, int t, int e, double mu, const LqrLds& m, int tid) {
+  constexpr int NT = 64 * NW;
+  const int nx = p.nx, nu = p.nu;
+  double *Vxx = m.Vxx, *Vx = m.Vx, *Qux = m.Qux, *Quu = m.Quu, *Qx = m.Qx, *Qu = m.Qu, *A = m.A, *Bt = m.B, *VA = m.VA, *VB = m.VB;
+  lqr_gemm_tn<NW>(nx, nx, nx, Vxx, nx, A, nx, 0, nullptr, 0, nullptr, 0, tid, [](int, int) { return 0.0; },
+                  [&](int r, int c, double v) { VA[r * nx + c] = v; });
+  lqr_gemm_tn<NW>(nx, nu, nx, Vxx, nx, Bt, nu, 0, nullptr, 0, nullptr, 0, tid, [](int, int) { return 0.0; },
+                  [&](int r, int c, double v) { VB[r * nu + c] = v; });
+  lqr_sync();
+
+  const double* lxx = p.lxx.p + (long)t * p.lxx.ss + (long)e * p.lxx.es;
+  const double* luu = p.luu.p + (long)t * p.luu.ss + (long)e * p.luu.es;
+  const double* lux = p.lux.p ? p.lux.p + (long)t * p.lux.ss + (long)e * p.lux.es : nullptr;
+  lqr_gemm_tn<NW>(nx, nx, nx, A, nx, VA, nx, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return lxx[r * nx + c]; },
+                  [&](int r, int c, double v) { Vxx[r * nx + c] = v; });
+  lqr_gemm_tn<NW>(nu, nx, nx, Bt, nu, VA, nx, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return lux ? lux[r * nx + c] : 0.0; },
+                  [&](int r, int c, double v) { Qux[r * nx + c] = v; });
+  lqr_gemm_tn<NW>(nu, nu, nx, Bt, nu, VB, nu, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return luu[r * nu + c] + (r == c ? mu : 0.0); },
+                  [&](int r, int c, double v) { Quu[r * nu + c] = v; });
+  const double* lx = p.lx.p + (long)t * p.lx.ss + (long)e * p.lx.es;
+  const double* lu = p.lu.p + (long)t * p.lu.ss + (long)e * p.lu.es;
+  for (int i = tid; i < nx + nu; i += NT) {
+    if (i < nx) {
+      double s = lx[i];
+      for (int k = 0; k < nx; k++) s = fma(A[k * nx + i], Vx[k], s);
+      Qx[i] = s;
+    } else {
+      const int a = i - nx;
+      double s = lu[a];
+      for (int k = 0; k < nx; k++) s = fma(Bt[k * nu + a], Vx[k], s);
+      Qu[a] = s;
+    }
+  }
+  lqr_sync();
+}
+
+// Cholesky Qw = L L^T, right-looking, one barrier per column: column j of the factor goes to L while every thread forms the
+// entries of it that its own trailing updates need from Qw's column j (same operations, same values).  false at a pivot that is
+// <= 0 or not finite - uniform: every thread reads the same pivot.
+template <int NT>
+MJB_LQR_DEV bool lqr_cholesky(double* Qw, double* Lf, int nu, int tid) {
+  constexpr int ldl = kLqrMaxNu;
+  for (int j = 0; j < nu; j++) {
+    const double d = Qw[j * nu + j];
+    if (!(d > 0.0) || !(d <= 1.7976931348623157e308)) return false;
+    const double s = sqrt(d);
+    for (int i = tid; i < nu * nu; i += NT) {
+      const int r = i / nu, c = i % nu;
+      if (r < j || c < j || c > r) continue;
+      if (c == j) Lf[r * ldl + j] = r == j ? s : Qw[r * nu + j] / s;
+      else Qw[r * nu + c] -= (Qw[r * nu + j] / s) * (Qw[c * nu + j] / s);
+    }
+    lqr_sync();
+  }
+  return true;
+}
+
+// L L^T x = column c of R, the column in registers: forward, backward, then store(i, -x[i]) for every row
+template <int MU, class Store>
+MJB_LQR_DEV void lqr_solve_column(const double* R, int ldr, const double* Lf, int nu, int c, Store store) {
+  constexpr int ldl = kLqrMaxNu;
+  double x[MU];
+#pragma unroll
+  for (int i = 0; i < MU; i++) x[i] = i < nu ? R[i * ldr + c] : 0.0;
+#pragma unroll
+  for (int j = 0; j < MU; j++) {
+    if (j < nu) {
+      x[j] = x[j] / Lf[j * ldl + j];
+#pragma unroll
+      for (int i = j + 1; i < MU; i++) if (i < nu) x[i] = fma(-Lf[i * ldl + j], x[j], x[i]);
+    }
+  }
+#pragma unroll
+  for (int j = MU - 1; j >= 0; j--) {
+    if (j < nu) {
+      x[j] = x[j] / Lf[j * ldl + j];
+#pragma unroll
+      for (int i = 0; i < j; i++) x[i] = fma(-Lf[j * ldl + i], x[j], x[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < MU; i++) if (i < nu) store(i, -x[i]);
+}
+
+// A pivot that is <= 0 or not finite at step t: reported, not propagated - zeros for the steps not solved and for the value terms,
+// 1 + t in status
+template <int NT>
+MJB_LQR_DEV void lqr_report_pivot(const LqrBackwardArgs& p, int t, int e, int tid) {
+  const int nx = p.nx, nu = p.nu;
+  for (int s = 0; s <= t; s++) {
+    double* ko = p.k + ((long)s * p.B + e) * nu;
+    double* Ko = p.K + ((long)s * p.B + e) * nu * nx;
+    for (int i = tid; i < nu; i += NT) ko[i] = 0.0;
+    for (int i = tid; i < nu * nx; i += NT) Ko[i] = 0.0;
+  }
+  if (p.V0x) for (int i = tid; i < nx; i += NT) p.V0x[(long)e * nx + i] = 0.0;
+  if (p.V0xx) for (int i = tid; i < nx * nx; i += NT) p.V0xx[(long)e * nx * nx + i] = 0.0;
+  if (tid == 0) { p.dV[2 * e] = 0.0; p.dV[2 * e + 1] = 0.0; p.status[e] = 1 + t; }
+}
+
+// With R = [K | k]: S = Quu K + Qux, wq = Quu k; Vxx = Qxx + K^T S + Qux^T K (every lane reads and writes its own elements of Vxx),
+// Vx = Qx + K^T (wq + Qu) + Qux^T k, and thread 0 adds the step's k^T Qu, k^T Quu k / 2 to dV1, dV2
+template <int NW>
+MJB_LQR_DEV void lqr_value_update(int nx, int nu, const LqrLds& m, int tid, double& dV1, double& dV2) {
+  constexpr int NT = 64 * NW;
+  const int ldr = nx + 1;
+  double *Vxx = m.Vxx, *Vx = m.Vx, *Qux = m.Qux, *Quu = m.Quu, *Qx = m.Qx, *Qu = m.Qu, *wq = m.wq, *R = m.R, *S = m.S;
+  lqr_gemm_tn<NW>(nu, nx, nu, Quu, nu, R, ldr, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return Qux[r * nx + c]; },
+                  [&](int r, int c, double v) { S[r * nx + c] = v; });
+  for (int a = tid; a < nu; a += NT) {
+    double s = 0.0;
+    for (int b = 0; b < nu; b++) s = fma(Quu[a * nu + b], R[b * ldr + nx], s);
+    wq[a] = s;
+  }
+  lqr_sync();
+
+  lqr_gemm_tn<NW>(nx, nx, nu, R, ldr, S, nx, nu, Qux, nx, R, ldr, tid, [&](int r, int c) { return Vxx[r * nx + c]; },
+                  [&](int r, int c, double v) { Vxx[r * nx + c] = v; });
+  for (int i = tid; i < nx; i += NT) {
+    double s = Qx[i];
+    for (int a = 0; a < nu; a++) s = fma(R[a * ldr + i], wq[a] + Qu[a], s);
+    for (int a = 0; a < nu; a++) s = fma(Qux[a * nx + i], R[a * ldr + nx], s);
+    Vx[i] = s;
+  }
+  if (tid == 0) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int a = 0; a < nu; a++) { s1 = fma(R[a * ldr + nx], Qu[a], s1); s2 = fma(R[a * ldr + nx], wq[a], s2); }
+    dV1 += s1; dV2 += 0.5 * s2;
+  }
+  lqr_sync();
+}
+
+// Vxx <- (Vxx + Vxx^T) / 2, and the next step's blocks from the registers into LDS (K, S are no longer read)
+template <int NT, int PA, int PB>
+MJB_LQR_DEV void lqr_step_end(int nx, int nu, const LqrLds& m, int tid, const double (&ra)[PA], const double (&rb)[PB]) {
+  double *Vxx = m.Vxx, *A = m.A, *Bt = m.B;
+  for (int i = tid; i < nx * nx; i += NT) {
+    const int r = i / nx, c = i % nx;
+    if (c < r) { const double v = 0.5 * (Vxx[r * nx + c] + Vxx[c * nx + r]); Vxx[r * nx + c] = v; Vxx[c * nx + r] = v; }
+  }
+#pragma unroll
+  for (int n = 0; n < PA; n++) { const int i = tid + n * NT; if (i < nx * nx) A[i] = ra[n]; }
+#pragma unroll
+  for (int n = 0; n < PB; n++) { const int i = tid + n * NT; if (i < nx * nu) Bt[i] = rb[n]; }
+  lqr_sync();
+}
+
 // ---- the backward recursion of environment e ---------------------------------------------------------------------------------
 // NW waves (64 NW threads, tid), nu <= MU (the unroll bound of the substitutions), w: the workgroup's LDS (lqr_layout(nx, nu).total doubles).
 template <int NW, int MU>
 MJB_LQR_DEV void lqr_backward_env(const LqrBackwardArgs& p, int e, int tid, double* w) {
   constexpr int NT = 64 * NW, PA = NW == 4 ? 16 : 4, PB = 8;     // PA, PB: elements of A_t, B_t one thread carries (nx <= 16 with one wave)
   const int nx = p.nx, nu = p.nu, T = p.T, ldr = nx + 1;
-  constexpr int ldl = kLqrMaxNu;
-  const LqrLay l = lqr_layout(nx, nu);
-  double *Vxx = w + l.Vxx, *Vx = w + l.Vx, *Qux = w + l.Qux, *Quu = w + l.Quu, *Qx = w + l.Qx, *Qu = w + l.Qu, *wq = w + l.wq;
-  double *A = w + l.A, *Bt = w + l.B, *VA = w + l.VA, *VB = w + l.VB, *Qw = w + l.Qw, *Lf = w + l.L, *R = w + l.R, *S = w + l.S;
-  const double* Ag = p.A.p + (long)e * p.A.es;
-  const double* Bg = p.Bm.p + (long)e * p.Bm.es;
+  const LqrLds m = lqr_lds_pointers(w, lqr_layout(nx, nu));
+  double *R = m.R;
   const double mu = p.mu.p[(long)e * p.mu.es];
   double dV1 = 0.0, dV2 = 0.0;                                   // carried by thread 0
-
-  for (int i = tid; i < nx * nx; i += NT) Vxx[i] = p.VxxT.p[(long)e * p.VxxT.es + i];
-  for (int i = tid; i < nx; i += NT) Vx[i] = p.VxT.p[(long)e * p.VxT.es + i];
-  for (int i = tid; i < nx * nx; i += NT) A[i] = Ag[(long)(T - 1) * p.A.ss + i];
-  for (int i = tid; i < nx * nu; i += NT) Bt[i] = Bg[(long)(T - 1) * p.Bm.ss + i];
-  lqr_sync();
+  lqr_load_terminal<NT>(p, e, m, tid);
 
   for (int t = T - 1; t >= 0; t--) {
-    // the next step's blocks: issued now, written to LDS at the end of this step
     double ra[PA], rb[PB];
-#pragma unroll
-    for (int n = 0; n < PA; n++) { const int i = tid + n * NT; ra[n] = (t > 0 && i < nx * nx) ? Ag[(long)(t - 1) * p.A.ss + i] : 0.0; }
-#pragma unroll
-    for (int n = 0; n < PB; n++) { const int i = tid + n * NT; rb[n] = (t > 0 && i < nx * nu) ? Bg[(long)(t - 1) * p.Bm.ss + i] : 0.0; }
-
-    // VA = Vxx A, VB = Vxx B
-    lqr_gemm_tn<NW>(nx, nx, nx, Vxx, nx, A, nx, 0, nullptr, 0, nullptr, 0, tid, [](int, int) { return 0.0; },
-                    [&](int r, int c, double v) { VA[r * nx + c] = v; });
-    lqr_gemm_tn<NW>(nx, nu, nx, Vxx, nx, Bt, nu, 0, nullptr, 0, nullptr, 0, tid, [](int, int) { return 0.0; },
-                    [&](int r, int c, double v) { VB[r * nu + c] = v; });
-    lqr_sync();
-
-    // Qxx = lxx + A^T VA (into Vxx, which nothing reads any more), Qux = lux + B^T VA, Quu = luu + B^T VB + mu I, Qx, Qu
-    {
-      const double* lxx = p.lxx.p + (long)t * p.lxx.ss + (long)e * p.lxx.es;
-      const double* luu = p.luu.p + (long)t * p.luu.ss + (long)e * p.luu.es;
-      const double* lux = p.lux.p ? p.lux.p + (long)t * p.lux.ss + (long)e * p.lux.es : nullptr;
-      lqr_gemm_tn<NW>(nx, nx, nx, A, nx, VA, nx, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return lxx[r * nx + c]; },
-                      [&](int r, int c, double v) { Vxx[r * nx + c] = v; });
-      lqr_gemm_tn<NW>(nu, nx, nx, Bt, nu, VA, nx, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return lux ? lux[r * nx + c] : 0.0; },
-                      [&](int r, int c, double v) { Qux[r * nx + c] = v; });
-      lqr_gemm_tn<NW>(nu, nu, nx, Bt, nu, VB, nu, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return luu[r * nu + c] + (r == c ? mu : 0.0); },
-                      [&](int r, int c, double v) { Quu[r * nu + c] = v; });
-      const double* lx = p.lx.p + (long)t * p.lx.ss + (long)e * p.lx.es;
-      const double* lu = p.lu.p + (long)t * p.lu.ss + (long)e * p.lu.es;
-      for (int i = tid; i < nx + nu; i += NT) {
-        if (i < nx) {
-          double s = lx[i];
-          for (int k = 0; k < nx; k++) s = fma(A[k * nx + i], Vx[k], s);
-          Qx[i] = s;
-        } else {
-          const int a = i - nx;
-          double s = lu[a];
-          for (int k = 0; k < nx; k++) s = fma(Bt[k * nu + a], Vx[k], s);
-          Qu[a] = s;
-        }
-      }
-    }
-    lqr_sync();
+    lqr_prefetch<NT>(p, t, e, tid, ra, rb);
+    lqr_step_products<NW>(p, t, e, mu, m, tid);
 
     // the solve's working set (it overlays A, B, VA, VB): Qw = Quu, R = [Qux | Qu]
-    for (int i = tid; i < nu * nu; i += NT) Qw[i] = Quu[i];
-    for (int i = tid; i < nu * ldr; i += NT) { const int a = i / ldr, c = i % ldr; R[i] = c < nx ? Qux[a * nx + c] : Qu[a]; }
+    for (int i = tid; i < nu * nu; i += NT) m.Qw[i] = m.Quu[i];
+    for (int i = tid; i < nu * ldr; i += NT) { const int a = i / ldr, c = i % ldr; R[i] = c < nx ? m.Qux[a * nx + c] : m.Qu[a]; }
+    lqr_sync();
+    if (!lqr_cholesky<NT>(m.Qw, m.L, nu, tid)) { lqr_report_pivot<NT>(p, t, e, tid); return; }
+
+    // L L^T X = R, one thread per right-hand side: R <- -X = [K | k]
+    double* ko = p.k + ((long)t * p.B + e) * nu;
+    double* Ko = p.K + ((long)t * p.B + e) * nu * nx;
+    for (int c = tid; c < ldr; c += NT)
+      lqr_solve_column<MU>(R, ldr, m.L, nu, c, [&](int i, double v) {
+        R[i * ldr + c] = v;
+        if (c < nx) Ko[i * nx + c] = v; else ko[i] = v;
+      });
     lqr_sync();
 
-    // Cholesky Quu = L L^T, right-looking, one barrier per column: column j of the factor goes to L while every thread forms the
-    // entries of it that its own trailing updates need from Qw's column j (same operations, same values)
-    bool bad = false;
-    for (int j = 0; j < nu; j++) {
-      const double d = Qw[j * nu + j];
-      if (!(d > 0.0) || !(d <= 1.7976931348623157e308)) { bad = true; break; }       // uniform: every thread reads the same pivot
-      const double s = sqrt(d);
-      for (int i = tid; i < nu * nu; i += NT) {
-        const int r = i / nu, c = i % nu;
-        if (r < j || c < j || c > r) continue;
-        if (c == j) Lf[r * ldl + j] = r == j ? s : Qw[r * nu + j] / s;
-        else Qw[r * nu + c] -= (Qw[r * nu + j] / s) * (Qw[c * nu + j] / s);
+    lqr_value_update<NW>(nx, nu, m, tid, dV1, dV2);
+    lqr_step_end<NT>(nx, nu, m, tid, ra, rb);
+  }
+  if (p.V0x) for (int i = tid; i < nx; i += NT) p.V0x[(long)e * nx + i] = m.Vx[i];
+  if (p.V0xx) for (int i = tid; i < nx * nx; i += NT) p.V0xx[(long)e * nx * nx + i] = m.Vxx[i];
+  if (tid == 0) { p.dV[2 * e] = dV1; p.dV[2 * e + 1] = dV2; p.status[e] = 0; }
+}
+
+// ---- the control-limited recursion of environment e (mjb_lqr_backward_box) ------------------------------------------------------
+// Per step the box QP  min x' Quu x / 2 + Qu' x,  lob <= x <= hib  (lob = lo - u_t, hib = hi - u_t) by projected Newton (Tassa,
+// Mansard, Todorov, ICRA 2014), then the step of lqr_backward_env with the clamped controls taken out of the solve.  The free block is
+// never gathered: lqr_solve_face replaces the clamped rows and columns of Qw by identity and zeroes those rows of R, so the Cholesky
+// and the substitution above run as they are, give on the free entries bitwise the compact factorisation, and with nothing clamped are
+// the unconstrained arithmetic itself.  Every decision that encloses a barrier (the clamped set, feasibility, the trial accepted, a
+// bad pivot) is read by every thread from the same LDS words after a barrier: workgroup-uniform.
+MJB_LQR_DEV double lqr_clip(double v, double lo, double hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+template <int NW, int MU>
+MJB_LQR_DEV void lqr_backward_box_env(const LqrBoxArgs& q, int e, int tid, double* w) {
+  constexpr int NT = 64 * NW, PA = NW == 4 ? 16 : 4, PB = 8;
+  const LqrBackwardArgs& p = q.b;
+  const int nx = p.nx, nu = p.nu, T = p.T, ldr = nx + 1;
+  const LqrBoxLay bl = lqr_box_layout(nx, nu);
+  const LqrLds m = lqr_lds_pointers(w, bl.l);
+  double *R = m.R, *Quu = m.Quu, *Qu = m.Qu;
+  double *X = w + bl.x, *XS = w + bl.xs, *G = w + bl.g, *LOB = w + bl.lob, *HIB = w + bl.hib, *CF = w + bl.cf, *FE = w + bl.fe, *PASS = w + bl.pass;
+  const unsigned full = nu >= 32 ? 0xffffffffu : (1u << nu) - 1u;
+  const double mu = p.mu.p[(long)e * p.mu.es];
+  const double lo_a = (q.lo && tid < nu) ? q.lo[tid] : -__builtin_huge_val();      // thread a < nu keeps the bounds of control a
+  const double hi_a = (q.hi && tid < nu) ? q.hi[tid] : __builtin_huge_val();
+  const double* ug = q.u.p + (long)e * q.u.es;
+  double dV1 = 0.0, dV2 = 0.0;
+  int failed = 0, itmax = 0;                                     // -(1 + t) of the highest step whose QP did not converge; the largest iteration count
+  lqr_load_terminal<NT>(p, e, m, tid);
+
+  // g = Qu + Quu x and the clamped set of x: (x == lob & g > 0) | (x == hib & g < 0), as a bit mask every thread holds
+  auto clamped_set = [&]() -> unsigned {
+    for (int a = tid; a < nu; a += NT) {
+      double s = Qu[a];
+      for (int b = 0; b < nu; b++) s = fma(Quu[a * nu + b], X[b], s);
+      G[a] = s;
+      CF[a] = ((X[a] == LOB[a] && s > 0.0) || (X[a] == HIB[a] && s < 0.0)) ? 1.0 : 0.0;
+    }
+    lqr_sync();
+    unsigned c = 0;
+    for (int a = 0; a < nu; a++) if (CF[a] != 0.0) c |= 1u << a;
+    return c;
+  };
+  // R <- [K | k] of the face x_c = X_c: K_f, k_f = -Quu_ff^-1 [Qux_f | Qu_f + Quu_fc x_c], K_c = 0, k_c = x_c.  false at a bad pivot.
+  auto solve_face = [&](unsigned c) -> bool {
+    for (int i = tid; i < nu * nu; i += NT) {
+      const int r = i / nu, cc = i % nu;
+      m.Qw[i] = (((c >> r) | (c >> cc)) & 1u) ? (r == cc ? 1.0 : 0.0) : Quu[i];
+    }
+    for (int i = tid; i < nu * ldr; i += NT) {
+      const int a = i / ldr, cc = i % ldr;
+      double v = 0.0;
+      if (!((c >> a) & 1u)) {
+        if (cc < nx) v = m.Qux[a * nx + cc];
+        else {
+          v = Qu[a];
+          for (int b = 0; b < nu; b++) if ((c >> b) & 1u) v = fma(Quu[a * nu + b], X[b], v);
+        }
+      }
+      R[i] = v;
+    }
+    lqr_sync();
+    if (!lqr_cholesky<NT>(m.Qw, m.L, nu, tid)) return false;
+    for (int cc = tid; cc < ldr; cc += NT)
+      lqr_solve_column<MU>(R, ldr, m.L, nu, cc, [&](int i, double v) { R[i * ldr + cc] = ((c >> i) & 1u) ? (cc < nx ? 0.0 : X[i]) : v; });
+    lqr_sync();
+    return true;
+  };
+  auto report_pivot = [&](int t) {
+    lqr_report_pivot<NT>(p, t, e, tid);
+    for (int s = tid; s <= t; s += NT) q.clamped[(long)s * p.B + e] = 0;
+    if (tid == 0) q.qp_iters[e] = itmax;
+  };
+
+  for (int t = T - 1; t >= 0; t--) {
+    double ra[PA], rb[PB];
+    lqr_prefetch<NT>(p, t, e, tid, ra, rb);
+    const double ru = tid < nu ? ug[(long)t * q.u.ss + tid] : 0.0;
+    lqr_step_products<NW>(p, t, e, mu, m, tid);
+
+    // the QP's box and starting point (they overlay A, B, VA, VB, as the solve's working set does): x = clip(0, lob, hib)
+    if (tid < nu) {
+      const double lob = lo_a - ru, hib = hi_a - ru;
+      LOB[tid] = lob; HIB[tid] = hib; X[tid] = lqr_clip(0.0, lob, hib);
+    }
+    lqr_sync();
+    unsigned c = clamped_set();
+    int iters = 0;
+    bool solved = false, stuck = false;                          // solved: R holds the face of the final set; stuck: a cap or a failed search
+    for (;;) {
+      iters++;
+      if (c == full) break;                                      // no free control
+      if (!solve_face(c)) { if (iters > itmax) itmax = iters; report_pivot(t); return; }
+      // the Newton target x* (a point, not an increment): taken whole when it lies in the box
+      if (tid < nu) {
+        const double v = R[tid * ldr + nx];
+        XS[tid] = v;
+        FE[tid] = lqr_clip(v, LOB[tid], HIB[tid]) == v ? 1.0 : 0.0;
       }
       lqr_sync();
-    }
-    if (bad) {
-      // reported, not propagated: zeros for the steps not solved and for the value terms, 1 + t in status
-      for (int s = 0; s <= t; s++) {
-        double* ko = p.k + ((long)s * p.B + e) * nu;
-        double* Ko = p.K + ((long)s * p.B + e) * nu * nx;
-        for (int i = tid; i < nu; i += NT) ko[i] = 0.0;
-        for (int i = tid; i < nu * nx; i += NT) Ko[i] = 0.0;
-      }
-      if (p.V0x) for (int i = tid; i < nx; i += NT) p.V0x[(long)e * nx + i] = 0.0;
-      if (p.V0xx) for (int i = tid; i < nx * nx; i += NT) p.V0xx[(long)e * nx * nx + i] = 0.0;
-      if (tid == 0) { p.dV[2 * e] = 0.0; p.dV[2 * e + 1] = 0.0; p.status[e] = 1 + t; }
-      return;
-    }
-
-    // L L^T X = R, one thread per right-hand side, the column in registers: forward, backward, then R <- -X = [K | k]
-    for (int c = tid; c < ldr; c += NT) {
-      double x[MU];
-#pragma unroll
-      for (int i = 0; i < MU; i++) x[i] = i < nu ? R[i * ldr + c] : 0.0;
-#pragma unroll
-      for (int j = 0; j < MU; j++) {
-        if (j < nu) {
-          x[j] = x[j] / Lf[j * ldl + j];
-#pragma unroll
-          for (int i = j + 1; i < MU; i++) if (i < nu) x[i] = fma(-Lf[i * ldl + j], x[j], x[i]);
+      bool inside = true;
+      for (int a = 0; a < nu; a++) if (FE[a] == 0.0) inside = false;
+      if (inside) {
+        if (tid < nu) X[tid] = XS[tid];
+        lqr_sync();
+        const unsigned c2 = clamped_set();
+        if (c2 == c) { solved = true; break; }                   // the same set at x*: done, tolerance-free
+        c = c2;
+      } else {
+        // Armijo search on clip(x + s (x* - x)), s = 0.6^j: trial j on thread j, the first that passes is the serial search's
+        if (tid < kLqrQpTrials) {
+          double sdotg = 0.0, fold = 0.0, fnew = 0.0, s = 1.0;
+          for (int j = 0; j < tid; j++) s *= 0.6;
+          for (int a = 0; a < nu; a++) sdotg = fma(G[a], XS[a] - X[a], sdotg);
+          for (int a = 0; a < nu; a++) {
+            double h0 = 0.0, h1 = 0.0;
+            for (int b = 0; b < nu; b++) {
+              const double yb = lqr_clip(X[b] + s * (XS[b] - X[b]), LOB[b], HIB[b]);
+              h0 = fma(Quu[a * nu + b], X[b], h0); h1 = fma(Quu[a * nu + b], yb, h1);
+            }
+            const double ya = lqr_clip(X[a] + s * (XS[a] - X[a]), LOB[a], HIB[a]);
+            fold = fma(X[a], Qu[a] + 0.5 * h0, fold); fnew = fma(ya, Qu[a] + 0.5 * h1, fnew);
+          }
+          PASS[tid] = (sdotg < 0.0 && fnew - fold <= 0.1 * s * sdotg) ? 1.0 : 0.0;
         }
-      }
-#pragma unroll
-      for (int j = MU - 1; j >= 0; j--) {
-        if (j < nu) {
-          x[j] = x[j] / Lf[j * ldl + j];
-#pragma unroll
-          for (int i = 0; i < j; i++) x[i] = fma(-Lf[j * ldl + i], x[j], x[i]);
+        lqr_sync();
+        int first = -1;
+        for (int j = kLqrQpTrials - 1; j >= 0; j--) if (PASS[j] != 0.0) first = j;
+        if (first < 0) { stuck = true; break; }                  // the search failed: keep the iterate
+        if (tid < nu) {
+          double s = 1.0;
+          for (int j = 0; j < first; j++) s *= 0.6;
+          X[tid] = lqr_clip(X[tid] + s * (XS[tid] - X[tid]), LOB[tid], HIB[tid]);
         }
+        lqr_sync();
+        c = clamped_set();
       }
-      double* ko = p.k + ((long)t * p.B + e) * nu;
-      double* Ko = p.K + ((long)t * p.B + e) * nu * nx;
-#pragma unroll
-      for (int i = 0; i < MU; i++) {
-        if (i < nu) {
-          R[i * ldr + c] = -x[i];
-          if (c < nx) Ko[i * nx + c] = -x[i]; else ko[i] = -x[i];
-        }
-      }
+      if (iters == kLqrQpIters) { stuck = true; break; }
     }
+    if (iters > itmax) itmax = iters;
+    if (stuck && !failed) failed = -(1 + t);
+    // the polish: one solve on the final set (already in R when the QP ended on it), k = clip(k, lob, hib)
+    if (!solved && !solve_face(c)) { report_pivot(t); return; }
+    double* ko = p.k + ((long)t * p.B + e) * nu;
+    double* Ko = p.K + ((long)t * p.B + e) * nu * nx;
+    if (tid < nu) {
+      const double v = lqr_clip(R[tid * ldr + nx], LOB[tid], HIB[tid]);
+      R[tid * ldr + nx] = v; ko[tid] = v;
+    }
+    for (int i = tid; i < nu * nx; i += NT) Ko[i] = R[(i / nx) * ldr + i % nx];
+    if (tid == 0) q.clamped[(long)t * p.B + e] = (int)c;
     lqr_sync();
 
-    // S = Quu K + Qux, wq = Quu k
-    lqr_gemm_tn<NW>(nu, nx, nu, Quu, nu, R, ldr, 0, nullptr, 0, nullptr, 0, tid, [&](int r, int c) { return Qux[r * nx + c]; },
-                    [&](int r, int c, double v) { S[r * nx + c] = v; });
-    for (int a = tid; a < nu; a += NT) {
-      double s = 0.0;
-      for (int b = 0; b < nu; b++) s = fma(Quu[a * nu + b], R[b * ldr + nx], s);
-      wq[a] = s;
-    }
-    lqr_sync();
-
-    // Vxx = Qxx + K^T S + Qux^T K (every lane reads and writes its own elements of Vxx), Vx = Qx + K^T (wq + Qu) + Qux^T k, dV
-    lqr_gemm_tn<NW>(nx, nx, nu, R, ldr, S, nx, nu, Qux, nx, R, ldr, tid, [&](int r, int c) { return Vxx[r * nx + c]; },
-                    [&](int r, int c, double v) { Vxx[r * nx + c] = v; });
-    for (int i = tid; i < nx; i += NT) {
-      double s = Qx[i];
-      for (int a = 0; a < nu; a++) s = fma(R[a * ldr + i], wq[a] + Qu[a], s);
-      for (int a = 0; a < nu; a++) s = fma(Qux[a * nx + i], R[a * ldr + nx], s);
-      Vx[i] = s;
-    }
-    if (tid == 0) {
-      double s1 = 0.0, s2 = 0.0;
-      for (int a = 0; a < nu; a++) { s1 = fma(R[a * ldr + nx], Qu[a], s1); s2 = fma(R[a * ldr + nx], wq[a], s2); }
-      dV1 += s1; dV2 += 0.5 * s2;
-    }
-    lqr_sync();
-
-    // Vxx <- (Vxx + Vxx^T) / 2, and the next step's blocks from the registers into LDS (K, S are no longer read)
-    for (int i = tid; i < nx * nx; i += NT) {
-      const int r = i / nx, c = i % nx;
-      if (c < r) { const double v = 0.5 * (Vxx[r * nx + c] + Vxx[c * nx + r]); Vxx[r * nx + c] = v; Vxx[c * nx + r] = v; }
-    }
-#pragma unroll
-    for (int n = 0; n < PA; n++) { const int i = tid + n * NT; if (i < nx * nx) A[i] = ra[n]; }
-#pragma unroll
-    for (int n = 0; n < PB; n++) { const int i = tid + n * NT; if (i < nx * nu) Bt[i] = rb[n]; }
-    lqr_sync();
+    lqr_value_update<NW>(nx, nu, m, tid, dV1, dV2);
+    lqr_step_end<NT>(nx, nu, m, tid, ra, rb);
   }
-  if (p.V0x) for (int i = tid; i < nx; i += NT) p.V0x[(long)e * nx + i] = Vx[i];
-  if (p.V0xx) for (int i = tid; i < nx * nx; i += NT) p.V0xx[(long)e * nx * nx + i] = Vxx[i];
-  if (tid == 0) { p.dV[2 * e] = dV1; p.dV[2 * e + 1] = dV2; p.status[e] = 0; }
+  if (p.V0x) for (int i = tid; i < nx; i += NT) p.V0x[(long)e * nx + i] = m.Vx[i];
+  if (p.V0xx) for (int i = tid; i < nx * nx; i += NT) p.V0xx[(long)e * nx * nx + i] = m.Vxx[i];
+  if (tid == 0) { p.dV[2 * e] = dV1; p.dV[2 * e + 1] = dV2; p.status[e] = failed; q.qp_iters[e] = itmax; }
 }
 
 // ---- the candidate controls of environment e, every step size --------------------------------------------------------------
@@ -439,6 +678,7 @@ MJB_LQR_DEV void lqr_candidates_env(const LqrCandArgs& p, int e, int tid, double
 #ifndef MJB_HOST_EMU
 // enqueue only (mjb_lqr.hip); the entry points (mjb_api.hip) have checked every pointer and extent
 hipError_t lqr_launch_backward(const LqrBackwardArgs& p, hipStream_t stream);
+hipError_t lqr_launch_backward_box(const LqrBoxArgs& p, hipStream_t stream);
 hipError_t lqr_launch_candidates(const LqrCandArgs& p, hipStream_t stream);
 hipError_t lqr_launch_gemm_probe(int M, int N, int K, const double* a, const double* b, double* c, hipStream_t stream);
 #endif

@@ -7,6 +7,7 @@ With ``rollout`` and ``linearize_rollout`` these are the phases of an iLQR itera
     state, _, A, B = linearize_rollout(model, data, u, initial_state=x0)       # A [B, T, nx, nx], B [B, T, nx, nu]
     c = trajectory_cost(data, state, u, initial_state=x0, Q=Q, R=R, Qf=Qf, x_ref=x_ref)       # cost [B], lx, lu, VxT
     sol = lqr_backward(data, A, B, lx=c.lx, lu=c.lu, lxx=Q, luu=R, VxT=c.VxT, VxxT=Qf, mu=1e-6)
+    # (with actuator limits: lqr_backward(..., u=u, lo=-u_max, hi=u_max) - the control-limited pass, an LqrBoxResult)
     cand = lqr_candidates(data, A, B, sol.k, sol.K, u, alphas, lo=-u_max, hi=u_max)        # [B, nalpha, T, nu]
     st, _ = rollout(model, search, cand[0], initial_state=x0)
     cc = trajectory_cost(search, st, cand[0], initial_state=x0, Q=Q, R=R, Qf=Qf, x_ref=x_ref, gradients=False)
@@ -36,6 +37,17 @@ class LqrBackwardResult(NamedTuple):
     V0x: object      # [B, nx]
     V0xx: object     # [B, nx, nx]
     status: object   # [B] int32: 0, or 1 + t for the first (highest) step whose Quu was not positive definite (results zeroed)
+
+
+class LqrBoxResult(NamedTuple):
+    k: object        # [B, T, nu] feed-forward terms, inside [lo - u, hi - u]; bitwise the bound where clamped
+    K: object        # [B, T, nu, nx] gains; the rows of clamped controls are zero
+    dV: object       # [B, 2]
+    V0x: object      # [B, nx]
+    V0xx: object     # [B, nx, nx]
+    status: object   # [B] int32: 0; 1 + t as LqrBackwardResult; -(1 + t) for the highest step whose QP did not converge (results usable)
+    clamped: object  # [B, T] int32: bit a set when control a is clamped at that step
+    qp_iters: object  # [B] int32: the largest QP iteration count of any step
 
 
 def _sim(data):
@@ -71,7 +83,24 @@ def _strided(fn, name, x, trail, B, T, dev, time_major, optional=False, dtypes=N
     return x.data_ptr(), ss, es, x
 
 
-def lqr_backward(data, A, B, *, lx=None, lu=None, lxx, luu, lux=None, VxT=None, VxxT, mu=1e-6, time_major: bool = False) -> LqrBackwardResult:
+def _bound(fn, name, x, nu, dev, keep):
+    """Device address of one side of a control box: a number, a float64 ``[nu]`` tensor, or ``None`` (0: unbounded on that side)."""
+    import torch
+
+    if x is None:
+        return 0
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.float64 or x.device != dev or tuple(x.shape) != (nu,):
+            raise ConfigError(f"{fn}: {name} must be a number or a float64 tensor [{nu}] on {dev}")
+        x = x.contiguous()
+    else:
+        x = torch.full((nu,), float(x), dtype=torch.float64, device=dev)
+    keep.append(x)
+    return x.data_ptr()
+
+
+def lqr_backward(data, A, B, *, lx=None, lu=None, lxx, luu, lux=None, VxT=None, VxxT, mu=1e-6, time_major: bool = False,
+                 u=None, lo=None, hi=None):
     """The Riccati / iLQR backward recursion for every trajectory, one kernel launch.  For ``t = T-1 .. 0`` from ``Vx = VxT, Vxx = VxxT``::
 
         Qx = lx + A' Vx    Qu = lu + B' Vx    Qxx = lxx + A' Vxx A    Quu = luu + B' Vxx B + mu I    Qux = lux + B' Vxx A
@@ -85,7 +114,15 @@ def lqr_backward(data, A, B, *, lx=None, lu=None, lxx, luu, lux=None, VxT=None, 
     number of trajectories is ``A``'s and need not be the data's batch.
 
     A trajectory whose ``Quu`` is not positive definite at some step stops there: ``status`` holds ``1 + t``, its ``k``, ``K`` of the
-    steps ``<= t``, ``dV``, ``V0x``, ``V0xx`` are zeros and the other trajectories are unaffected (raise ``mu`` and call again)."""
+    steps ``<= t``, ``dV``, ``V0x``, ``V0xx`` are zeros and the other trajectories are unaffected (raise ``mu`` and call again).
+
+    **Control limits.**  With ``lo`` and / or ``hi`` (a number, a ``[nu]`` tensor or ``None`` = unbounded on that side, as
+    ``lqr_candidates`` takes them) and the nominal controls ``u [B, T, nu]`` (required then, read in place), the pass is control-limited
+    DDP (Tassa, Mansard, Todorov 2014; ``mjb_lqr_backward_box``): per step the box QP ``min dk' Quu dk / 2 + Qu' dk`` subject to
+    ``lo - u_t <= dk <= hi - u_t`` by projected Newton, ``k`` its solution (bitwise the bound where clamped), the rows of ``K`` of the
+    clamped controls zero, the value update unchanged.  Returns an ``LqrBoxResult``: the fields above plus ``clamped [B, T]`` (bit
+    masks) and ``qp_iters [B]``; ``status`` may also be ``-(1 + t)``: the QP of step ``t`` hit its iteration cap (64) or its line search
+    failed, the results are still inside the box.  With both bounds ``None`` the call is the unconstrained one above."""
     import torch
 
     fn = "lqr_backward"
@@ -125,17 +162,33 @@ def lqr_backward(data, A, B, *, lx=None, lu=None, lxx, luu, lux=None, VxT=None, 
         mu = torch.full((1,), float(mu), dtype=torch.float64, device=dev)
         arrays["mu"] = (mu.data_ptr(), 0, 0)
     keep.append(mu)
+    box = lo is not None or hi is not None
+    bounds = {}
+    if box:
+        p, ss, es, t = _strided(fn, "u", u, (nu,), nb, T, dev, time_major)
+        if tuple(t.shape) == (nu,):
+            raise ConfigError(f"{fn}: u must have shape {[T, nb, nu] if time_major else [nb, T, nu]}")
+        arrays["u"] = (p, ss, es); keep.append(t)
+        bounds = {"lo": _bound(fn, "lo", lo, nu, dev, keep), "hi": _bound(fn, "hi", hi, nu, dev, keep)}
     opt = dict(dtype=torch.float64, device=dev)
     k = torch.empty((T, nb, nu), **opt)
     K = torch.empty((T, nb, nu, nx), **opt)
     dV, V0x, V0xx = torch.empty((nb, 2), **opt), torch.empty((nb, nx), **opt), torch.empty((nb, nx, nx), **opt)
     status = torch.empty((nb,), dtype=torch.int32, device=dev)
-    sim.lqr_backward({"T": T, "batch": nb, "nx": nx, "nu": nu}, arrays,
-                     {"k": k.data_ptr(), "K": K.data_ptr(), "dV": dV.data_ptr(), "V0x": V0x.data_ptr(), "V0xx": V0xx.data_ptr(),
-                      "status": status.data_ptr()}, keep=keep)
+    sizes = {"T": T, "batch": nb, "nx": nx, "nu": nu}
+    ptrs = {"k": k.data_ptr(), "K": K.data_ptr(), "dV": dV.data_ptr(), "V0x": V0x.data_ptr(), "V0xx": V0xx.data_ptr(), "status": status.data_ptr()}
+    if not box:
+        sim.lqr_backward(sizes, arrays, ptrs, keep=keep)
+        if not time_major:
+            k, K = k.permute(1, 0, 2), K.permute(1, 0, 2, 3)
+        return LqrBackwardResult(k, K, dV, V0x, V0xx, status)
+    clamped = torch.empty((T, nb), dtype=torch.int32, device=dev)
+    qp_iters = torch.empty((nb,), dtype=torch.int32, device=dev)
+    ptrs.update(bounds, clamped=clamped.data_ptr(), qp_iters=qp_iters.data_ptr())
+    sim.lqr_backward_box(sizes, arrays, ptrs, keep=keep)
     if not time_major:
-        k, K = k.permute(1, 0, 2), K.permute(1, 0, 2, 3)
-    return LqrBackwardResult(k, K, dV, V0x, V0xx, status)
+        k, K, clamped = k.permute(1, 0, 2), K.permute(1, 0, 2, 3), clamped.permute(1, 0)
+    return LqrBoxResult(k, K, dV, V0x, V0xx, status, clamped, qp_iters)
 
 
 def lqr_candidates(data, A, B, k, K, u, alphas, *, dx0=None, lo=None, hi=None, dtype=None, time_major: bool = False):
@@ -172,18 +225,7 @@ def lqr_candidates(data, A, B, k, K, u, alphas, *, dx0=None, lo=None, hi=None, d
             raise ConfigError(f"{fn}: dx0 must be a float64 tensor [{nb}, {nx}] or [{nx}] on {dev}")
         dx0 = dx0.contiguous()
         arrays["dx0"] = (dx0.data_ptr(), 0, nx if dx0.ndim == 2 else 0); keep.append(dx0)
-    ptrs = {"alphas": alphas.data_ptr()}
-    for name, x in (("lo", lo), ("hi", hi)):
-        if x is None:
-            ptrs[name] = 0
-            continue
-        if isinstance(x, torch.Tensor):
-            if x.dtype != torch.float64 or x.device != dev or tuple(x.shape) != (nu,):
-                raise ConfigError(f"{fn}: {name} must be a number or a float64 tensor [{nu}] on {dev}")
-            x = x.contiguous()
-        else:
-            x = torch.full((nu,), float(x), dtype=torch.float64, device=dev)
-        ptrs[name] = x.data_ptr(); keep.append(x)
+    ptrs = {"alphas": alphas.data_ptr(), "lo": _bound(fn, "lo", lo, nu, dev, keep), "hi": _bound(fn, "hi", hi, nu, dev, keep)}
     cand = torch.empty((nb, na, T, nu), dtype=dtype, device=dev)
     ptrs["cand"] = cand.data_ptr()
     sim.lqr_candidates({"T": T, "batch": nb, "nx": nx, "nu": nu, "nalpha": na, "out_f32": int(dtype == torch.float32)}, arrays, ptrs,
@@ -348,4 +390,4 @@ def select_candidates(data, cost, cand, *, mode: str = "argmin", temperature=Non
     return TrajSelectResult(u, best, best_cost, weights)
 
 
-__all__ = ["LqrBackwardResult", "lqr_backward", "lqr_candidates", "TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]
+__all__ = ["LqrBackwardResult", "LqrBoxResult", "lqr_backward", "lqr_candidates", "TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]

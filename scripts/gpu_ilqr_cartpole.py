@@ -13,10 +13,13 @@ Each iteration (horizon T, one nominal control sequence):
              the per-iteration costs stay on the GPU and are read once at the end - apart from the synchronises that close the timed
              phases, an iteration never waits for the GPU.  --cost torch: the einsum cost, ``xs @ Q`` / ``u @ R`` / ``Qf @ xs[T]`` and
              a host ``argmin``, as before.
+  limits     --limits clamp (the default): the backward pass does not know the actuator limit U_MAX, only the candidates are clamped
+             to it; --limits box: ``lqr_backward(..., u=u, lo=-U_MAX, hi=U_MAX)``, the control-limited pass (zero gains and the bound
+             itself as feed-forward for a saturated control), and the same clamped candidates.
 The pole starts tilted by --tilt rad; the cost asks for the upright pole at the origin.  Prints one JSON line: cost per iteration,
 the tilt at the end of the final trajectory and the wall time of each phase (each closed by a device synchronise).
 
-    python scripts/gpu_ilqr_cartpole.py [--horizon 100] [--iters 15] [--alphas 16] [--tilt 0.3] [--backward kernel|torch] [--cost kernel|torch] [--out FILE.json]
+    python scripts/gpu_ilqr_cartpole.py [--horizon 100] [--iters 15] [--alphas 16] [--tilt 0.3] [--backward kernel|torch] [--cost kernel|torch] [--limits clamp|box] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -45,8 +48,13 @@ def main():
     ap.add_argument("--tilt", type=float, default=0.3)
     ap.add_argument("--backward", choices=("kernel", "torch"), default="kernel")
     ap.add_argument("--cost", choices=("kernel", "torch"), default=None, help="default: kernel with --backward kernel, torch otherwise")
+    ap.add_argument("--limits", choices=("clamp", "box"), default="clamp",
+                    help="clamp: the backward pass ignores U_MAX and the candidates are clamped to it; box: the control-limited backward pass "
+                         "(lqr_backward with u, lo, hi) as well; needs --backward kernel")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.limits == "box" and args.backward != "kernel":
+        raise SystemExit("--limits box is the kernel's control-limited pass: it needs --backward kernel")
     if args.cost is None:
         args.cost = "kernel" if args.backward == "kernel" else "torch"
     if args.cost == "kernel" and args.backward != "kernel":
@@ -82,6 +90,8 @@ def main():
     Qt[0] = 0
     Qt1, QtK = Qt[None], Qt[None].expand(K, T, nx, nx)
     cost_dev = torch.zeros(args.iters + 1, dtype=f64, device=dev)
+    limits = dict(u=None, lo=-U_MAX, hi=U_MAX) if args.limits == "box" else {}
+    clamped_steps = []                                                         # --limits box: per iteration, the steps whose control is clamped (a device tensor each)
     for it in range(args.iters):
         t0 = time.perf_counter()
         state, _, A, Bm = linearize_rollout(model, nominal, u, initial_state=x0)
@@ -90,7 +100,11 @@ def main():
         if args.cost == "kernel":
             c0 = trajectory_cost(nominal, state, u, initial_state=x0_dev, Q=Qt1, R=R, Qf=Qf, x_ref=x_goal)
             cost_dev[it:it + 1].copy_(c0.cost)
-            sol = lqr_backward(nominal, A, Bm, lx=c0.lx, lu=c0.lu, lxx=Qt1, luu=R, VxT=c0.VxT, VxxT=Qf, mu=reg)
+            if limits:
+                limits["u"] = u
+            sol = lqr_backward(nominal, A, Bm, lx=c0.lx, lu=c0.lu, lxx=Qt1, luu=R, VxT=c0.VxT, VxxT=Qf, mu=reg, **limits)
+            if limits:
+                clamped_steps.append((sol.clamped != 0).sum())
             torch.cuda.synchronize()
             t2 = time.perf_counter()
             cand = lqr_candidates(nominal, A, Bm, sol.k, sol.K, u, alphas, lo=-U_MAX, hi=U_MAX)
@@ -108,7 +122,11 @@ def main():
             lx[0] = 0                                                          # the script's cost has no state term at t = 0
             lxx = Q.expand(T, nx, nx).clone()
             lxx[0] = 0
-            sol = lqr_backward(nominal, A, Bm, lx=lx[None], lu=u @ R, lxx=lxx[None], luu=R, VxT=Qf @ xs[T], VxxT=Qf, mu=reg)
+            if limits:
+                limits["u"] = u
+            sol = lqr_backward(nominal, A, Bm, lx=lx[None], lu=u @ R, lxx=lxx[None], luu=R, VxT=Qf @ xs[T], VxxT=Qf, mu=reg, **limits)
+            if limits:
+                clamped_steps.append((sol.clamped != 0).sum())
         else:
             A, Bm = A[0], Bm[0]
             Vx, Vxx = Qf @ xs[T], Qf.clone()
@@ -145,7 +163,8 @@ def main():
         costs = cost_dev.tolist()                                              # the one host read of the costs
     else:
         costs.append(float(cost(state, u)[0]))
-    res = {"backward": args.backward, "cost": args.cost, "horizon": T, "iterations": args.iters, "alphas": K, "tilt0_rad": args.tilt, "cost_per_iteration": costs,
+    res = {"backward": args.backward, "cost": args.cost, "limits": args.limits, "u_max": U_MAX, "clamped_steps_per_iteration": [int(c) for c in clamped_steps],
+           "iterations_to_within_1e-3_of_final": next(i for i, c in enumerate(costs) if c <= costs[-1] * (1 + 1e-3)), "horizon": T, "iterations": args.iters, "alphas": K, "tilt0_rad": args.tilt, "cost_per_iteration": costs,
            "final_tilt_rad": float(state[0, -1, 2]), "final_slider_m": float(state[0, -1, 1]),
            "wall_s": {k: v for k, v in split.items()}, "wall_share": {k: v / sum(split.values()) for k, v in split.items()}}
     print(json.dumps(res), flush=True)

@@ -1,0 +1,242 @@
+"""The control-limited backward pass (``mjb_lqr_backward_box``) without a GPU: the kernel source (``mjb_lqr.hpp``) compiled for the
+host (``tests/lqr_box_host.cpp``, the emulation of ``tests/lqr_host.cpp``) against the numpy restatement of ``tests/lqr_box_common.py``
+(long double = truth, float64 = the measure of the bound: 8 x its own error, floor 1e-13), its exact structure, its reduction to the
+unconstrained recursion, an enumeration of active sets that owes nothing to the restatement, an indefinite ``Quu``, the LDS layout,
+and the cross-compilation for gfx950."""
+from __future__ import annotations
+
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import lqr_box_common as bc
+from tests import lqr_common as lc
+from tests.test_lqr_host import BackwardArgs, Strided
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+SIZES = [(4, 1, 200), (7, 3, 64), (12, 4, 100), (16, 12, 20), (54, 21, 10), (64, 32, 6)]
+
+
+class BoxArgs(ctypes.Structure):
+    _fields_ = [("b", BackwardArgs), ("u", Strided)] + [(n, ctypes.c_void_p) for n in ("lo", "hi", "clamped", "qp_iters")]
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("lqr_box") / "liblqr_box_host.so")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", so,
+                           os.path.join(HERE, "lqr_box_host.cpp")])
+    lib = ctypes.CDLL(so)
+    lib.lqrbh_lds_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.lqrbh_lds_bytes.restype = ctypes.c_long
+    return lib
+
+
+def _base(p, out, luu=None, mu=None):
+    T, B, nx, nu = p["A"].shape[0], p["A"].shape[1], p["A"].shape[2], p["B"].shape[3]
+    luu = np.ascontiguousarray(p["R"] if luu is None else luu)
+    mu = np.ascontiguousarray(np.broadcast_to(np.asarray(p["mu"] if mu is None else mu, dtype=np.float64), (B,)))
+    keep = {k: np.ascontiguousarray(p[k]) for k in ("A", "B", "lx", "lu", "Q", "VxT", "VxxT")}
+    keep["luu"], keep["mu"] = luu, mu
+    a = BackwardArgs(T=T, B=B, nx=nx, nu=nu)
+    S = lambda x, ss, es: Strided(x.ctypes.data, ss, es)
+    a.A, a.Bm = S(keep["A"], B * nx * nx, nx * nx), S(keep["B"], B * nx * nu, nx * nu)
+    a.lx, a.lu = S(keep["lx"], B * nx, nx), S(keep["lu"], B * nu, nu)
+    a.lxx, a.luu, a.lux = S(keep["Q"], 0, nx * nx), S(luu, 0, nu * nu), Strided(None, 0, 0)
+    a.VxT, a.VxxT, a.mu = S(keep["VxT"], 0, nx), S(keep["VxxT"], 0, nx * nx), S(mu, 0, 1)
+    for k in ("k", "K", "dV", "V0x", "V0xx", "status"):
+        setattr(a, k, out[k].ctypes.data)
+    return a, keep
+
+
+def _outputs(T, B, nx, nu):
+    return {"k": np.full((T, B, nu), np.nan), "K": np.full((T, B, nu, nx), np.nan), "dV": np.full((B, 2), np.nan),
+            "V0x": np.full((B, nx), np.nan), "V0xx": np.full((B, nx, nx), np.nan), "status": np.full(B, -7777, dtype=np.int32),
+            "clamped": np.full((T, B), -7777, dtype=np.int32), "qp_iters": np.full(B, -7777, dtype=np.int32)}
+
+
+def _batch_major(out):
+    out["k"], out["K"] = out["k"].transpose(1, 0, 2), out["K"].transpose(1, 0, 2, 3)
+    if "clamped" in out:
+        out["clamped"] = out["clamped"].T
+    return out
+
+
+def host_box(lib, p, lo="p", hi="p", luu=None, mu=None):
+    """The emulated kernel on a ``box_inputs`` dict; lo / hi: "p" = the dict's, an array, or None (NULL).  Outputs [B, T, ...]."""
+    T, B, nx, nu = p["A"].shape[0], p["A"].shape[1], p["A"].shape[2], p["B"].shape[3]
+    out = _outputs(T, B, nx, nu)
+    a = BoxArgs()
+    a.b, keep = _base(p, out, luu, mu)
+    u = np.ascontiguousarray(p["u"])
+    lo = p["lo"] if isinstance(lo, str) else lo
+    hi = p["hi"] if isinstance(hi, str) else hi
+    lo, hi = (None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (lo, hi))
+    a.u = Strided(u.ctypes.data, B * nu, nu)
+    a.lo, a.hi = (None if x is None else x.ctypes.data for x in (lo, hi))
+    a.clamped, a.qp_iters = out["clamped"].ctypes.data, out["qp_iters"].ctypes.data
+    assert lib.lqrbh_backward_box(ctypes.byref(a)) == 0
+    return _batch_major(out)
+
+
+def host_unconstrained(lib, p, luu=None, mu=None):
+    T, B, nx, nu = p["A"].shape[0], p["A"].shape[1], p["A"].shape[2], p["B"].shape[3]
+    out = {k: v for k, v in _outputs(T, B, nx, nu).items() if k not in ("clamped", "qp_iters")}
+    a, keep = _base(p, out, luu, mu)
+    assert lib.lqrbh_backward(ctypes.byref(a)) == 0
+    return _batch_major(out)
+
+
+case = bc.case
+
+
+def check_structure(got, p):
+    """k is bitwise the bound where clamped and inside the box everywhere; the clamped rows of K are zero.  got [B, T, ...]."""
+    nu = p["lo"].shape[0]
+    u = p["u"].transpose(1, 0, 2)
+    lob, hib = p["lo"][None, None] - u, p["hi"][None, None] - u
+    cm = ((got["clamped"][..., None].view(np.uint32) >> np.arange(nu, dtype=np.uint32)) & 1).astype(bool)
+    assert cm.any() and not cm.all()
+    at_lo, at_hi = got["k"] == lob, got["k"] == hib
+    assert (at_lo | at_hi)[cm].all()
+    assert (got["k"] >= lob).all() and (got["k"] <= hib).all()
+    assert (got["K"][cm] == 0).all() and (np.abs(got["K"][~cm]).max(axis=-1) > 0).all()
+    return cm
+
+
+# ---- 1, 2. the recursion against the restatement, and its exact structure -------------------------------------------------------------
+@pytest.mark.parametrize("b", bc.BOUNDS)
+@pytest.mark.parametrize("nx,nu,T", SIZES)
+def test_box_recursion_matches_the_restatement(driver, nx, nu, T, b):
+    p, truth, f64 = case(nx, nu, T, b)
+    bc.preconditions(truth, f64)
+    got = host_box(driver, p)
+    assert (got["status"] == 0).all()
+    assert np.array_equal(got["clamped"], truth["clamped"])
+    assert ((got["qp_iters"] >= 1) & (got["qp_iters"] <= bc.QP_MAX_ITER)).all()
+    for key in lc.OUTPUTS:
+        mine, numpy64 = lc.rel_err(got[key], truth[key]), lc.rel_err(f64[key], truth[key])
+        print(f"{(nx, nu, T, b)} {key}: kernel {mine:.2e}  float64 numpy {numpy64:.2e}  iters {got['qp_iters'].tolist()}")
+        assert mine <= lc.bound(numpy64), (key, mine, numpy64)
+
+
+@pytest.mark.parametrize("b", bc.BOUNDS)
+@pytest.mark.parametrize("nx,nu,T", SIZES)
+def test_exact_structure(driver, nx, nu, T, b):
+    p, truth, f64 = case(nx, nu, T, b)
+    bc.preconditions(truth, f64)
+    cm = check_structure(host_box(driver, p), p)
+    assert np.array_equal(cm, truth["cmask"])
+
+
+# ---- 3. unbounded is unconstrained ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("how", ["null", "inf"])
+@pytest.mark.parametrize("nx,nu,T", [(4, 1, 30), (7, 3, 20), (16, 12, 8), (54, 21, 4)])
+def test_unbounded_is_the_unconstrained_recursion_bitwise(driver, nx, nu, T, how):
+    p = bc.box_inputs(nx, nu, T, 2, 0.5)
+    lo, hi = (None, None) if how == "null" else (np.full(nu, -np.inf), np.full(nu, np.inf))
+    got, ref = host_box(driver, p, lo=lo, hi=hi), host_unconstrained(driver, p)
+    for key in lc.OUTPUTS + ("status",):
+        assert np.array_equal(got[key], ref[key]), key
+    assert (ref["status"] == 0).all() and np.isfinite(ref["K"]).all()
+    assert (got["clamped"] == 0).all() and (got["qp_iters"] == 1).all()
+
+
+# ---- 4. independent of the restatement ----------------------------------------------------------------------------------------------------
+def test_single_step_qp_against_enumeration_of_active_sets(driver):
+    """T = 1, nu = 3: with VxT = 0 and VxxT given, Quu = R + B' VxxT B + mu I and Qu = lu, so the kernel's k must be the QP's solution,
+    found here by trying all 27 active sets in long double."""
+    nx, nu, B = 5, 3, 64
+    p = bc.box_inputs(nx, nu, 1, B, 0.5)
+    rng = np.random.default_rng(11)
+    p["lu"] = rng.normal(size=(1, B, nu))                        # gradients large enough to press against the box
+    M = rng.normal(size=(B, nu, nu))
+    p["R"] = 0.3 * np.einsum("bij,bkj->bik", M, M) + 0.05 * np.eye(nu)[None]        # coupled controls: a diagonal Quu would make every QP separable
+    got = host_box(driver, p)
+    assert (got["status"] == 0).all()
+    ld = np.longdouble
+    nclamped = 0
+    worst, worst64 = 0.0, 0.0
+    for e in range(B):
+        Bt, Vxx = p["B"][0, e].astype(ld), p["VxxT"][e].astype(ld)
+        Quu = p["R"][e].astype(ld) + Bt.T @ Vxx @ Bt + ld(p["mu"]) * np.eye(nu, dtype=ld)
+        lob, hib = p["lo"] - p["u"][0, e], p["hi"] - p["u"][0, e]
+        x = bc.enumerate_qp(Quu, p["lu"][0, e], lob, hib)
+        x64, _, _, how, _ = bc.box_qp(Quu.astype(np.float64), p["lu"][0, e].copy(), lob, hib)
+        assert how == "ok"
+        nclamped += int(((x == lob) | (x == hib)).sum())
+        worst, worst64 = max(worst, lc.rel_err(got["k"][e, 0], x)), max(worst64, lc.rel_err(x64, x))
+    print(f"enumeration: kernel {worst:.2e}  float64 numpy QP {worst64:.2e}  clamped {nclamped} of {B * nu}")
+    assert 0.2 * B * nu < nclamped < 0.8 * B * nu
+    assert worst <= lc.bound(worst64), (worst, worst64)
+
+
+# ---- 5. an indefinite Quu ---------------------------------------------------------------------------------------------------------------
+def test_indefinite_quu_is_reported_as_before(driver):
+    nx, nu, T, B, badenv = 7, 3, 12, 5, 2
+    p = bc.box_inputs(nx, nu, T, B, 0.5)
+    luu = p["R"].copy(); luu[badenv] = -np.eye(nu)
+    mu = np.full(B, p["mu"]); mu[badenv] = 0.0
+    got = host_box(driver, p, luu=luu, mu=mu)
+    assert got["status"].tolist() == [0, 0, T, 0, 0]
+    for key in lc.OUTPUTS + ("clamped",):
+        assert np.array_equal(got[key][badenv], np.zeros_like(got[key][badenv])), key
+    keep = [e for e in range(B) if e != badenv]
+    sub = {k: (v[:, keep] if k in ("A", "B", "lx", "lu", "u") else v[keep] if isinstance(v, np.ndarray) and k not in ("lo", "hi") else v) for k, v in p.items()}
+    alone = host_box(driver, sub)
+    for key in lc.OUTPUTS + ("status", "clamped", "qp_iters"):
+        assert np.array_equal(got[key][keep], alone[key]), key
+    assert (alone["clamped"] != 0).any()
+    assert all(np.isfinite(got[key]).all() for key in lc.OUTPUTS)
+
+
+def test_violated_or_nan_bounds_still_terminate(driver):
+    """lo > hi and a NaN input: the caps are compile-time constants, so the call returns; the trajectory whose QP cannot converge is
+    reported through a non-zero status, the other one is untouched by it."""
+    nx, nu, T = 7, 3, 6
+    p = bc.box_inputs(nx, nu, T, 2, 0.5)
+    got = host_box(driver, p, lo=np.full(nu, 0.5), hi=np.full(nu, -0.5))
+    assert got["status"].shape == (2,)
+    q = dict(p); q["lu"] = p["lu"].copy(); q["lu"][T - 2, 1, 0] = np.nan
+    got = host_box(driver, q)
+    assert got["status"][0] == 0 and got["status"][1] != 0
+    assert (got["qp_iters"] <= bc.QP_MAX_ITER).all()
+
+
+# ---- 6. layout ------------------------------------------------------------------------------------------------------------------------------
+def test_box_layout_is_disjoint_and_fits(driver):
+    for nx in (1, 2, 4, 7, 16, 17, 54, 64):
+        for nu in (1, 3, 8, 9, 21, 32):
+            assert driver.lqrbh_layout_ok(nx, nu) == 1, (nx, nu)
+            assert driver.lqrbh_lds_bytes(nx, nu) <= 160 * 1024, (nx, nu)
+
+
+# ---- 7. build -------------------------------------------------------------------------------------------------------------------------------
+def test_translation_unit_cross_compiles_with_the_box_kernel(tmp_path):
+    hipcc = "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.fail("hipcc is required: the kernels are HIP for gfx950")
+    src = os.path.join(ROOT, "mujoco_template_amd", "csrc", "mjb_lqr.hip")
+    asm = str(tmp_path / "mjb_lqr.s")
+    subprocess.check_call([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", asm, src])
+    text = open(asm).read()
+    assert text.count("k_lqr_backward_box") >= 3 and "k_lqr_backward" in text
+
+
+def test_library_exports_the_box_entry_point():
+    so = os.path.join(ROOT, "mujoco_template_amd", "libmjbatch.so")
+    if not os.path.exists(so):
+        import __graft_entry__ as g
+
+        g.build()
+    import torch  # noqa: F401  (one HIP runtime per process: torch first)
+
+    lib = ctypes.CDLL(so)
+    assert hasattr(lib, "mjb_lqr_backward_box")
+    import mujoco_template_amd as mt
+
+    assert mt.LqrBoxResult._fields == ("k", "K", "dV", "V0x", "V0xx", "status", "clamped", "qp_iters")
