@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mjbatch.h"
+#include "mjb_buffer.hpp"
 #include "mjb_host.hpp"
 #include "mjb_kernels.hpp"
 #include "mjb_lqr.hpp"
@@ -31,23 +32,28 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
     if (e_ != hipSuccess) return fail(MJB_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));      \
   } while (0)
 
-struct DevAlloc {
-  std::vector<void*> ptrs;
-  bool ok = true;
+struct DevAlloc {                                           // the model tables of fill_dev_model as blocks of the data object's arena
+  Arena& arena;
   template <typename X> const X* put(const std::vector<X>& v) {
-    size_t n = v.size() ? v.size() : 1;
-    void* p = nullptr;
-    if (hipMalloc(&p, n * sizeof(X)) != hipSuccess) { ok = false; return nullptr; }
-    ptrs.push_back(p);
-    if (v.size() && hipMemcpy(p, v.data(), v.size() * sizeof(X), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-    return (const X*)p;
+    X* p = arena.alloc<X>(v.size());
+    if (p && v.size() && hipMemcpy(p, v.data(), v.size() * sizeof(X), hipMemcpyHostToDevice) != hipSuccess) arena.ok = false;
+    return p;
   }
   const float* putf(const std::vector<float>& v) { return put(v); }
   const double* putf(const std::vector<double>& v) { return put(v); }
   const int* puti(const std::vector<int>& v) { return put(v); }
   const unsigned long long* putu(const std::vector<unsigned long long>& v) { return put(v); }
-  void release() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
 };
+// every block of a group that is allocated together: a failed call leaves the whole group empty, and the next call allocates again
+template <typename... B> void reset_all(B&... b) { (b.reset(), ...); }
+// the zero fill dev_alloc (below) gives an arena block, for a Buffer that has just been made or has grown
+template <typename X> hipError_t reserve_zeroed(Buffer<X>& b, size_t n) {
+  if (n <= b.count()) return hipSuccess;
+  hipError_t e = b.reserve(n);
+  if (e == hipSuccess && b.kind() != Mem::Device) std::memset(b.get(), 0, n * sizeof(X));
+  else if (e == hipSuccess && (e = hipMemset(b.get(), 0, n * sizeof(X))) != hipSuccess) b.reset();
+  return e;
+}
 
 struct ArrayInfo { void* ptr; long per_env; int kind; };  // kind: 0 = data dtype, 1 = float64, 2 = int32, 3 = uint32 (int32 to mjb_array_ptr, widened by mjb_get_array)
 }  // namespace
@@ -65,7 +71,7 @@ struct mjbModel {
 
 struct mjbObsSpec {
   ObsSpecDev dev;
-  std::vector<void*> owned;
+  Arena arena;                                              // the id tables dev points at
 };
 
 // Launch configuration of a data object (derive_config): lane-group widths, caps on contacts / constraint rows, LDS layouts
@@ -80,7 +86,7 @@ struct mjbData {
   int batch, dtype, device, env0;
   Config cfg;
   hipStream_t stream;
-  DevAlloc alloc;
+  Arena arena;                          // blocks of the object's whole life: model tables, descriptors, state and debug arrays
   DevModel<float> mf;
   DevModel<double> md;
   DevModel<float>* mf_dev = nullptr;    // device copies of the structs above and of the layouts (read through the constant address space)
@@ -94,15 +100,14 @@ struct mjbData {
   DevData<float> df;
   DevData<double> dd;
   std::map<std::string, ArrayInfo> arrays;
-  std::vector<void*> owned;
   // debug dumps
   bool dbg_ready = false;
   DevDebug<float> dbgf;
   DevDebug<double> dbgd;
   std::map<std::string, ArrayInfo> dbg_arrays;
   // device-side feedback controller gains (float and double copies): K [nu, 2nv], u0 [nu], q0 [nq], v0 [nv]
-  float* fbf[4] = {nullptr, nullptr, nullptr, nullptr};
-  double* fbd[4] = {nullptr, nullptr, nullptr, nullptr};
+  Buffer<float> fbf[4];
+  Buffer<double> fbd[4];
   // work scheduling of k_step (launch()): resident workgroups of the kernel in use on this device; < 0 = not yet queried
   long step_slots = -1;
   int sched_chunk = -1, fair_bit = -1;     // experiment overrides (MJB_CHUNK_STEPS, MJB_FAIR_BIT); -1 = policy below
@@ -110,40 +115,38 @@ struct mjbData {
   unsigned long long ticket_next = 0;      // value of the device ticket counter when the next ticket launch starts
   int last_sched[6] = {0, 0, 0, 0, 0, 0};  // of the last mode-0 launch: steps, environment blocks, resident slots, chunk_steps, fair_bit, two waves per environment
   // fd / jac scratch
-  double *fd_y = nullptr, *fd_A = nullptr, *fd_B = nullptr;  // fd_y / fd_valid: per-column scratch of fd_cap points (fd_scratch), grown on demand
-  size_t fd_cap = 0;
+  Buffer<double> fd_y, fd_A, fd_B; Buffer<int> fd_valid;       // fd_y / fd_valid: per-column scratch (fd_scratch), grown on demand
   hipEvent_t fd_done = nullptr;                                // recorded behind the last FD launch: a call on ANOTHER stream waits for it before it reuses the scratch
   hipStream_t fd_stream = nullptr; bool fd_pending = false;
   int last_fd_slabs = 0;                                       // slabs of the last mjb_transition_fd_points (mjb_fd_points_slabs)
-  double *fd_A_host = nullptr, *fd_B_host = nullptr;          // pinned: the (A, B) blocks leave the device in one async copy each
+  Buffer<double> fd_A_host{Mem::Pinned}, fd_B_host{Mem::Pinned};   // the (A, B) blocks leave the device in one async copy each
   // mjb_jac: persistent buffers (grown on demand) - the request (kinds | ids) in pinned memory the kernel reads directly, the result
   // blocks pinned (small requests: written by the kernel itself) and on the device (large requests: one async copy each)
-  void* io_pin = nullptr; size_t io_pin_cap = 0;               // pinned staging of mjb_get_array / mjb_set_array (grown on demand)
-  int* jac_req_pin = nullptr; int jac_req_cap = 0;
-  double *jac_pin[2] = {nullptr, nullptr}, *jac_dev[2] = {nullptr, nullptr};
-  size_t jac_pin_cap = 0, jac_dev_cap = 0;
-  int* fd_valid = nullptr;
+  Buffer<unsigned char> io_pin{Mem::Pinned};                   // pinned staging of mjb_get_array / mjb_set_array (grown on demand, with slack)
+  Buffer<int> jac_req_pin{Mem::Pinned};
+  Buffer<double> jac_pin[2] = {Buffer<double>(Mem::Pinned), Buffer<double>(Mem::Pinned)}, jac_dev[2];
   // standalone feedback law (mjb_feedback_ctrl): optional noise (std [nu], table [nsteps, nu]) in both precisions, dx scratch for float64
-  float *fb_noise_f[2] = {nullptr, nullptr};
-  double *fb_noise_d[2] = {nullptr, nullptr}, *fb_dx = nullptr;
+  Buffer<float> fb_noise_f[2];
+  Buffer<double> fb_noise_d[2], fb_dx;
   int fb_nsteps = 0, fb_env_stride = 0;
   // host mirror (mjb_host_view): ONE pinned float64 block  qpos | qvel | ctrl | qacc | qacc_warmstart | time , each [batch, n],
   // and its device staging twin; filled by one pack kernel + one D2H per mjb_sync_to_host
-  double *mirror_host = nullptr, *mirror_dev = nullptr;
-  double* mirror_shadow = nullptr;        // host copy of the block as last refreshed / uploaded: what in-place edits are detected against
+  Buffer<double> mirror_host{Mem::PinnedCoherent}, mirror_dev;
+  std::vector<double> mirror_shadow;      // host copy of the block as last refreshed / uploaded: what in-place edits are detected against
   unsigned long long mirror_seq = 0;      // sequence number of the last polled host-driven step (completion words behind the flags word)
   size_t mirror_off[7] = {0, 0, 0, 0, 0, 0, 0};             // element offsets of the six fields, [6] = total
-  int* flags_pin = nullptr;               // pinned: the four engine-flag bits as words the kernels set (DevData::flags_pin)
-  unsigned* episode = nullptr;            // [batch] resets per environment by mjb_reset_envs (the episode counter of its noise streams)
-  unsigned xfer_timeout = 0;              // ticks of the 100 MHz clock a wave waits for a hand-over (0 = not yet read from MJB_XFER_TIMEOUT_MS)
+  Buffer<int> flags_pin{Mem::Pinned};     // the four engine-flag bits as words the kernels set (DevData::flags_pin)
+  Buffer<unsigned> episode;               // [batch] resets per environment by mjb_reset_envs (the episode counter of its noise streams)
+  Buffer<unsigned long long> xfer;        // hand-over buffer of the ticket map (DevData<float>::xfer), made by the first launch that needs it
+  unsigned xfer_timeout = 0;             // ticks of the 100 MHz clock a wave waits for a hand-over (0 = not yet read from MJB_XFER_TIMEOUT_MS)
   int xfer_poison_env = -1;               // test hook MJB_XFER_POISON_ENV (-1 = not yet read)
   // per-environment model parameters (mjb_set_env_param): rows of slot k (PRM_*, mjb_types.hpp) in float64 and, for float32 data, fp32;
-  // the same pointers sit in df.prm / dd.prm, which the kernels receive
-  double* prm_d[PRM_NSLOT] = {};
-  float* prm_f[PRM_NSLOT] = {};
+  // the same pointers sit in df.prm / dd.prm, which the kernels receive (prm_publish)
+  Buffer<double> prm_d[PRM_NSLOT];
+  Buffer<float> prm_f[PRM_NSLOT];
   int prm_mask = 0;                       // bit k = field k batched
   int spec_prm[4] = {0, 0, 0, 0};         // the batched fields each loaded specialised kernel was built for
-  double* prm_stage = nullptr; size_t prm_stage_cap = 0;     // device staging of host-memory sources (float64)
+  Buffer<double> prm_stage;               // device staging of host-memory sources (float64)
 };
 
 namespace {
@@ -207,13 +210,9 @@ void h_quat_mul(double* r, const double* a, const double* b) {
 }
 
 template <typename X> int dev_alloc(mjbData* d, X** out, size_t n) {
-  void* p = nullptr;
   if (n == 0) n = 1;
-  if (hipMalloc(&p, n * sizeof(X)) != hipSuccess) return -1;
-  if (hipMemset(p, 0, n * sizeof(X)) != hipSuccess) return -1;
-  d->owned.push_back(p);
-  *out = (X*)p;
-  return 0;
+  *out = d->arena.alloc<X>(n);
+  return *out && hipMemset(*out, 0, n * sizeof(X)) == hipSuccess ? 0 : -1;
 }
 
 template <typename TS> int alloc_state(mjbData* d, DevData<TS>& s) {
@@ -229,11 +228,8 @@ template <typename TS> int alloc_state(mjbData* d, DevData<TS>& s) {
   rc |= dev_alloc(d, &s.qfrc_inverse, B * h.nv); rc |= dev_alloc(d, &s.actuator_moment, B * h.nu * h.nv);
   rc |= dev_alloc(d, &s.counters, B * CNT_N); rc |= dev_alloc(d, &s.flags, 1);
   rc |= dev_alloc(d, &s.sched, 1);
-  if (!d->flags_pin) {                                          // the engine flags as four words of pinned host memory (raise_engine_flags)
-    if (hipHostMalloc((void**)&d->flags_pin, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) return -1;
-    std::memset(d->flags_pin, 0, 4 * sizeof(int));
-  }
-  s.flags_pin = d->flags_pin;
+  if (reserve_zeroed(d->flags_pin, 4) != hipSuccess) return -1;   // the engine flags as four words of pinned host memory (raise_engine_flags)
+  s.flags_pin = d->flags_pin.get();
   s.xfer = nullptr;                                             // hand-over buffer of the ticket map: allocated by the first launch that needs it
   rc |= dev_alloc(d, &s.prof, (size_t)PH_N + 4 * B);        // + per-environment timeline records of the -DMJB_TIMELINE diagnostic kernel
   if (rc) return -1;
@@ -245,8 +241,8 @@ template <typename TS> int alloc_state(mjbData* d, DevData<TS>& s) {
   A["subtree_com"] = {s.subtree_com, h.nbody * 3L, 0}; A["sensordata"] = {s.sensordata, h.nsensordata, 0};
   A["qfrc_inverse"] = {s.qfrc_inverse, h.nv, 0}; A["actuator_moment"] = {s.actuator_moment, (long)h.nu * h.nv, 0};
   A["counters"] = {s.counters, CNT_N, 2};
-  if (dev_alloc(d, &d->episode, B)) return -1;
-  A["episode"] = {d->episode, 1, 3};
+  if (reserve_zeroed(d->episode, B) != hipSuccess) return -1;
+  A["episode"] = {d->episode.get(), 1, 3};
   return 0;
 }
 
@@ -560,7 +556,7 @@ static void choose_schedule(mjbData* d, StepArgs& a) {
 // synchronisation (and at the entry of the next launch) the host sees it without a copy: every entry point that synchronises
 // returns MJB_ERR_DEVICE from then on, until mjb_reset clears the flags.
 int engine_check(const mjbData* d) {
-  if (d->flags_pin && __atomic_load_n(d->flags_pin + 3, __ATOMIC_ACQUIRE) != 0)
+  if (d->flags_pin.get() && __atomic_load_n(d->flags_pin.get() + 3, __ATOMIC_ACQUIRE) != 0)
     return fail(MJB_ERR_DEVICE, "a ticket-mode launch timed out waiting for a state hand-over (engine flag 8): the environments concerned were not "
                                 "advanced; mjb_reset() clears the condition");
   return MJB_OK;
@@ -588,7 +584,8 @@ int launch(mjbData* d, const StepArgs& a_in, const ObsSpecDev& obs, void* obs_ou
   }
   if (a.chunk_steps > 0 && !d->df.xfer) {
     const HostModel& hm = d->model->h;
-    if (dev_alloc(d, &d->df.xfer, (size_t)d->batch * (size_t)(hm.nq + 3 * hm.nv + 2))) { d->df.xfer = nullptr; a.chunk_steps = 0; }   // no memory: static map
+    if (reserve_zeroed(d->xfer, (size_t)d->batch * (size_t)(hm.nq + 3 * hm.nv + 2)) != hipSuccess) a.chunk_steps = 0;   // no memory: static map
+    d->df.xfer = d->xfer.get();
   }
   if (a.chunk_steps > 0) chunk_plan_counts(a.nstep, a.chunk_steps, a.nuniform, a.nchunk);
   if (a.mode == 0) {
@@ -661,30 +658,19 @@ int launch(mjbData* d, const StepArgs& a_in, const ObsSpecDev& obs, void* obs_ou
 
 // pinned staging block of the array getters / setters: the copies run on the data's stream straight to / from pinned memory (no pageable
 // staging inside the runtime, no per-call temporary), the widening / narrowing conversion happens between it and the caller's array
-int ensure_io_pin(mjbData* d, size_t bytes) {
-  if (bytes <= d->io_pin_cap) return MJB_OK;
-  if (d->io_pin) (void)hipHostFree(d->io_pin);
-  d->io_pin = nullptr; d->io_pin_cap = 0;
-  const size_t cap = bytes < 4096 ? 4096 : bytes + bytes / 4;
-  HIPCHK(hipHostMalloc(&d->io_pin, cap, hipHostMallocDefault));
-  d->io_pin_cap = cap;
-  return MJB_OK;
-}
-
 int copy_out(mjbData* d, const ArrayInfo& ai, double* host_out) {
   size_t n = (size_t)d->batch * ai.per_env;
   if (n == 0) return MJB_OK;
   const bool wide = ai.kind == 1 || (ai.kind == 0 && d->dtype == MJB_F64);
   if (!wide && ai.kind != 0 && ai.kind != 3) return fail(MJB_ERR_ARG, "integer array requested as float64");
   const size_t bytes = n * (wide ? sizeof(double) : sizeof(float));
-  int rc = ensure_io_pin(d, bytes);
-  if (rc != MJB_OK) return rc;
-  HIPCHK(hipMemcpyAsync(d->io_pin, ai.ptr, bytes, hipMemcpyDeviceToHost, d->stream));   // ordered behind whatever the stream still runs
+  HIPCHK(d->io_pin.reserve(bytes, true));
+  HIPCHK(hipMemcpyAsync(d->io_pin.get(), ai.ptr, bytes, hipMemcpyDeviceToHost, d->stream));   // ordered behind whatever the stream still runs
   HIPCHK(hipStreamSynchronize(d->stream));
   { int ec = engine_check(d); if (ec != MJB_OK) return ec; }
-  if (ai.kind == 3) { const unsigned* src = (const unsigned*)d->io_pin; for (size_t i = 0; i < n; i++) host_out[i] = (double)src[i]; }
-  else if (wide) std::memcpy(host_out, d->io_pin, bytes);
-  else { const float* src = (const float*)d->io_pin; for (size_t i = 0; i < n; i++) host_out[i] = (double)src[i]; }
+  if (ai.kind == 3) { const unsigned* src = (const unsigned*)d->io_pin.get(); for (size_t i = 0; i < n; i++) host_out[i] = (double)src[i]; }
+  else if (wide) std::memcpy(host_out, d->io_pin.get(), bytes);
+  else { const float* src = (const float*)d->io_pin.get(); for (size_t i = 0; i < n; i++) host_out[i] = (double)src[i]; }
   return MJB_OK;
 }
 }  // namespace
@@ -740,9 +726,10 @@ int mjb_data_create(mjbModel* m, int batch, int dtype, int lanes, int nconmax, i
   mjbData* d = new mjbData();
   d->model = m; d->batch = batch; d->dtype = dtype; d->cfg = cfg; d->device = device; d->env0 = env0; d->stream = nullptr;
   if (hipDeviceGetAttribute(&d->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || d->ncu < 1) d->ncu = 256;
-  fill_dev_model<float>(h, d->alloc, cfg.ncon_max, cfg.nefc_max, d->mf);
-  fill_dev_model<double>(h, d->alloc, cfg.ncon_max, cfg.nefc_max, d->md);
-  if (!d->alloc.ok) { mjb_data_free(d); return fail(MJB_ERR_DEVICE, "device allocation of the model failed"); }
+  DevAlloc tables{d->arena};
+  fill_dev_model<float>(h, tables, cfg.ncon_max, cfg.nefc_max, d->mf);
+  fill_dev_model<double>(h, tables, cfg.ncon_max, cfg.nefc_max, d->md);
+  if (!d->arena.ok) { mjb_data_free(d); return fail(MJB_ERR_DEVICE, "device allocation of the model failed"); }
   if (dev_alloc(d, &d->mf_dev, 1) || dev_alloc(d, &d->md_dev, 1) || dev_alloc(d, &d->Lf_dev, 1) || dev_alloc(d, &d->Ld_dev, 1) || dev_alloc(d, &d->Lf2_dev, 1) ||
       hipMemcpy(d->Lf2_dev, &d->cfg.Lf2, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d->Lf_dev, &d->cfg.Lf, sizeof(Lay), hipMemcpyHostToDevice) != hipSuccess ||
@@ -763,22 +750,8 @@ void mjb_data_free(mjbData* d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
   for (auto& k : d->spec) if (k.mod) (void)hipModuleUnload(k.mod);
-  for (void* p : d->owned) (void)hipFree(p);
-  if (d->mirror_host) (void)hipHostFree(d->mirror_host);
-  std::free(d->mirror_shadow);
-  if (d->fd_y) (void)hipFree(d->fd_y);
-  if (d->fd_valid) (void)hipFree(d->fd_valid);
   if (d->fd_done) (void)hipEventDestroy(d->fd_done);
-  if (d->fd_A_host) (void)hipHostFree(d->fd_A_host);
-  if (d->fd_B_host) (void)hipHostFree(d->fd_B_host);
-  if (d->jac_req_pin) (void)hipHostFree(d->jac_req_pin);
-  if (d->io_pin) (void)hipHostFree(d->io_pin);
-  if (d->flags_pin) (void)hipHostFree(d->flags_pin);
-  for (int k = 0; k < 2; k++) { if (d->jac_pin[k]) (void)hipHostFree(d->jac_pin[k]); if (d->jac_dev[k]) (void)hipFree(d->jac_dev[k]); }
-  for (int k = 0; k < PRM_NSLOT; k++) { if (d->prm_d[k]) (void)hipFree(d->prm_d[k]); if (d->prm_f[k]) (void)hipFree(d->prm_f[k]); }
-  if (d->prm_stage) (void)hipFree(d->prm_stage);
-  d->alloc.release();
-  delete d;
+  delete d;                                                    // the arena and every Buffer member release their memory
 }
 
 int mjb_set_stream(mjbData* d, void* hip_stream) { if (!d) return fail(MJB_ERR_ARG, "data is NULL"); d->stream = (hipStream_t)hip_stream; return MJB_OK; }
@@ -787,16 +760,13 @@ int mjb_sync(mjbData* d) { if (!d) return fail(MJB_ERR_ARG, "data is NULL"); HIP
 int mjb_engine_flags(mjbData* d, int* flags_out) {
   if (!d || !flags_out) return fail(MJB_ERR_ARG, "NULL argument");
   HIPCHK(hipStreamSynchronize(d->stream));
-  int fl = 0;
-  for (int k = 0; k < 4; k++) if (d->flags_pin && __atomic_load_n(d->flags_pin + k, __ATOMIC_ACQUIRE) != 0) fl |= 1 << k;
-  *flags_out = fl;
-  return MJB_OK;
+  return mjb_engine_flags_peek(d, flags_out);
 }
 
 int mjb_engine_flags_peek(mjbData* d, int* flags_out) {
   if (!d || !flags_out) return fail(MJB_ERR_ARG, "NULL argument");
   int fl = 0;
-  for (int k = 0; k < 4; k++) if (d->flags_pin && __atomic_load_n(d->flags_pin + k, __ATOMIC_ACQUIRE) != 0) fl |= 1 << k;
+  for (int k = 0; k < 4; k++) if (d->flags_pin.get() && __atomic_load_n(d->flags_pin.get() + k, __ATOMIC_ACQUIRE) != 0) fl |= 1 << k;
   *flags_out = fl;
   return MJB_OK;
 }
@@ -841,11 +811,10 @@ int mjb_set_array(mjbData* d, const char* name, const double* host_in) {
   const bool wide = ai.kind == 1 || (ai.kind == 0 && d->dtype == MJB_F64);
   if (!wide && ai.kind != 0) return fail(MJB_ERR_ARG, "integer arrays are read-only");   // (counters, episode)
   const size_t bytes = n * (wide ? sizeof(double) : sizeof(float));
-  int rc = ensure_io_pin(d, bytes);
-  if (rc != MJB_OK) return rc;
-  if (wide) std::memcpy(d->io_pin, host_in, bytes);
-  else { float* dst = (float*)d->io_pin; for (size_t i = 0; i < n; i++) dst[i] = (float)host_in[i]; }
-  HIPCHK(hipMemcpyAsync(ai.ptr, d->io_pin, bytes, hipMemcpyHostToDevice, d->stream));    // ordered behind the launches already queued
+  HIPCHK(d->io_pin.reserve(bytes, true));
+  if (wide) std::memcpy(d->io_pin.get(), host_in, bytes);
+  else { float* dst = (float*)d->io_pin.get(); for (size_t i = 0; i < n; i++) dst[i] = (float)host_in[i]; }
+  HIPCHK(hipMemcpyAsync(ai.ptr, d->io_pin.get(), bytes, hipMemcpyHostToDevice, d->stream));    // ordered behind the launches already queued
   HIPCHK(hipStreamSynchronize(d->stream));                                               // the staging block is free again on return
   return MJB_OK;
 }
@@ -879,7 +848,7 @@ int mjb_reset(mjbData* d, int key) {
   HIPCHK(hipGetLastError());
   // a reset also clears the sticky engine flags (k_reset, in stream order); after a failed ticket launch the host-visible word must be
   // clear before the next launch's entry check reads it: wait for the reset in that (rare) case
-  if (d->flags_pin && __atomic_load_n(d->flags_pin + 3, __ATOMIC_ACQUIRE) != 0) HIPCHK(hipStreamSynchronize(d->stream));
+  if (d->flags_pin.get() && __atomic_load_n(d->flags_pin.get() + 3, __ATOMIC_ACQUIRE) != 0) HIPCHK(hipStreamSynchronize(d->stream));
   return MJB_OK;
 }
 
@@ -899,8 +868,8 @@ int mjb_reset_envs(mjbData* d, int key, const unsigned char* mask_dev, unsigned 
   r.time = key >= 0 ? h.D("key_time")[key] : 0.0;
   r.seed = seed; r.qpos_noise = qpos_noise; r.qvel_noise = qvel_noise;
   const int threads = 64, grid = (d->batch + threads - 1) / threads;
-  if (d->dtype == MJB_F32) hipLaunchKernelGGL(k_reset_envs<float>, dim3(grid), dim3(threads), 0, d->stream, d->df, r, mask_dev, (unsigned)d->env0, d->episode);
-  else hipLaunchKernelGGL(k_reset_envs<double>, dim3(grid), dim3(threads), 0, d->stream, d->dd, r, mask_dev, (unsigned)d->env0, d->episode);
+  if (d->dtype == MJB_F32) hipLaunchKernelGGL(k_reset_envs<float>, dim3(grid), dim3(threads), 0, d->stream, d->df, r, mask_dev, (unsigned)d->env0, d->episode.get());
+  else hipLaunchKernelGGL(k_reset_envs<double>, dim3(grid), dim3(threads), 0, d->stream, d->dd, r, mask_dev, (unsigned)d->env0, d->episode.get());
   HIPCHK(hipGetLastError());
   return MJB_OK;
 }
@@ -1022,16 +991,16 @@ int mjb_rollout(mjbData* d, int nstep, int ctrl_mode, unsigned seed, unsigned st
   if (!d) return fail(MJB_ERR_ARG, "data is NULL");
   if (nstep < 1) return fail(MJB_ERR_ARG, "nstep must be >= 1");
   if (ctrl_mode < 0 || ctrl_mode > 3) return fail(MJB_ERR_ARG, "bad ctrl_mode");
-  if (ctrl_mode == 3 && !d->fbd[0]) return fail(MJB_ERR_ARG, "MJB_CTRL_FEEDBACK needs mjb_set_feedback() first");
+  if (ctrl_mode == 3 && !d->fbd[0].get()) return fail(MJB_ERR_ARG, "MJB_CTRL_FEEDBACK needs mjb_set_feedback() first");
   HIPCHK(hipSetDevice(d->device));
   StepArgs a = make_args(d, nstep, ctrl_mode, seed, step0, ctrl_scale, 0);
   if (ctrl_mode == 3) {
-    if (d->dtype == MJB_F32) { a.fb_K = d->fbf[0]; a.fb_u0 = d->fbf[1]; a.fb_q0 = d->fbf[2]; a.fb_v0 = d->fbf[3]; }
-    else { a.fb_K = d->fbd[0]; a.fb_u0 = d->fbd[1]; a.fb_q0 = d->fbd[2]; a.fb_v0 = d->fbd[3]; }
+    if (d->dtype == MJB_F32) { a.fb_K = d->fbf[0].get(); a.fb_u0 = d->fbf[1].get(); a.fb_q0 = d->fbf[2].get(); a.fb_v0 = d->fbf[3].get(); }
+    else { a.fb_K = d->fbd[0].get(); a.fb_u0 = d->fbd[1].get(); a.fb_q0 = d->fbd[2].get(); a.fb_v0 = d->fbd[3].get(); }
     if (d->fb_nsteps > 0) {
       a.fb_nsteps = d->fb_nsteps; a.fb_env_stride = d->fb_env_stride;
-      a.fb_noise_std = d->dtype == MJB_F32 ? (const void*)d->fb_noise_f[0] : (const void*)d->fb_noise_d[0];
-      a.fb_noise_tab = d->dtype == MJB_F32 ? (const void*)d->fb_noise_f[1] : (const void*)d->fb_noise_d[1];
+      a.fb_noise_std = d->dtype == MJB_F32 ? (const void*)d->fb_noise_f[0].get() : (const void*)d->fb_noise_d[0].get();
+      a.fb_noise_tab = d->dtype == MJB_F32 ? (const void*)d->fb_noise_f[1].get() : (const void*)d->fb_noise_d[1].get();
     }
   }
   ObsSpecDev obs; std::memset(&obs, 0, sizeof(obs));
@@ -1196,8 +1165,8 @@ __global__ void k_prm_pair_friction(const double* gf, const int* g1, const int* 
 // the kernels' view of the rows (both DevData, so that a float32 data object's float64 FD kernel finds the masters)
 void prm_publish(mjbData* d) {
   for (int k = 0; k < PRM_NSLOT; k++) {
-    d->df.prm.d[k] = d->dd.prm.d[k] = (const double MJB_CONST*)d->prm_d[k];
-    d->df.prm.f[k] = d->dd.prm.f[k] = (const float MJB_CONST*)d->prm_f[k];
+    d->df.prm.d[k] = d->dd.prm.d[k] = (const double MJB_CONST*)d->prm_d[k].get();
+    d->df.prm.f[k] = d->dd.prm.f[k] = (const float MJB_CONST*)d->prm_f[k].get();
   }
 }
 // After the set of batched fields changed: the specialised kernels built for another set are unloaded (the generic kernels read the
@@ -1210,28 +1179,25 @@ int prm_mask_changed(mjbData* d) {
   for (int kind = 1; kind < 4; kind++) if (d->spec[kind].mod && d->spec_prm[kind] != d->prm_mask) drop_kernel(d, kind);
   return MJB_OK;
 }
-// rows of slot k, allocated and filled with the model's values for every environment
+void prm_free(mjbData* d, int k) { reset_all(d->prm_d[k], d->prm_f[k]); }
+// rows of slot k, allocated and filled with the model's values for every environment: both blocks of the slot, or neither
 int prm_alloc(mjbData* d, int k) {
-  if (d->prm_d[k]) return MJB_OK;
+  const bool f32 = d->dtype == MJB_F32;
+  if (d->prm_d[k].get() && (!f32 || d->prm_f[k].get())) return MJB_OK;
   std::vector<double> v;
   std::string err;
   if (!prm_model_values(d->model, k, v, err)) return fail(MJB_ERR_ARG, err);
   const size_t n = v.size(), total = (size_t)d->batch * n;
   std::vector<double> rows(total ? total : 1);
   for (size_t e = 0; e < (size_t)d->batch; e++) std::memcpy(rows.data() + e * n, v.data(), n * sizeof(double));
-  if (hipMalloc(&d->prm_d[k], rows.size() * sizeof(double)) != hipSuccess) { d->prm_d[k] = nullptr; return fail(MJB_ERR_DEVICE, "device allocation of parameter rows failed"); }
-  HIPCHK(hipMemcpy(d->prm_d[k], rows.data(), total * sizeof(double), hipMemcpyHostToDevice));
-  if (d->dtype == MJB_F32) {
-    std::vector<float> rf(rows.begin(), rows.end());
-    if (hipMalloc(&d->prm_f[k], rf.size() * sizeof(float)) != hipSuccess) { d->prm_f[k] = nullptr; return fail(MJB_ERR_DEVICE, "device allocation of parameter rows failed"); }
-    HIPCHK(hipMemcpy(d->prm_f[k], rf.data(), total * sizeof(float), hipMemcpyHostToDevice));
+  const std::vector<float> rf(rows.begin(), rows.end());
+  if (d->prm_d[k].reserve(rows.size()) != hipSuccess || (f32 && d->prm_f[k].reserve(rf.size()) != hipSuccess)) {
+    prm_free(d, k);
+    return fail(MJB_ERR_DEVICE, "device allocation of parameter rows failed");
   }
+  HIPCHK(hipMemcpy(d->prm_d[k].get(), rows.data(), total * sizeof(double), hipMemcpyHostToDevice));
+  if (f32) HIPCHK(hipMemcpy(d->prm_f[k].get(), rf.data(), total * sizeof(float), hipMemcpyHostToDevice));
   return MJB_OK;
-}
-void prm_free(mjbData* d, int k) {
-  if (d->prm_d[k]) (void)hipFree(d->prm_d[k]);
-  if (d->prm_f[k]) (void)hipFree(d->prm_f[k]);
-  d->prm_d[k] = nullptr; d->prm_f[k] = nullptr;
 }
 int prm_derived(int k) { return k == PRM_BODY_MASS ? PRM_SUBTREEMASS : (k == PRM_GEOM_FRICTION ? PRM_PAIR_FRICTION : -1); }
 }  // namespace
@@ -1265,30 +1231,27 @@ int mjb_set_env_param(mjbData* d, const char* name, const void* src, int src_dty
   int from_f32 = src_dtype == MJB_F32;
   if (!src_on_device) {                                        // host memory: through the pinned block to a device stage, read before return
     const size_t bytes = total * sizeof(double);
-    rc = ensure_io_pin(d, bytes);
-    if (rc != MJB_OK) return rc;
-    if (d->prm_stage_cap < bytes) {
-      if (d->prm_stage) { HIPCHK(hipStreamSynchronize(d->stream)); (void)hipFree(d->prm_stage); }
-      d->prm_stage = nullptr; d->prm_stage_cap = 0;
-      HIPCHK(hipMalloc(&d->prm_stage, bytes));
-      d->prm_stage_cap = bytes;
+    HIPCHK(d->io_pin.reserve(bytes, true));
+    if (d->prm_stage.count() < total) {
+      if (d->prm_stage.get()) HIPCHK(hipStreamSynchronize(d->stream));   // kernels already queued may still read the old stage
+      HIPCHK(d->prm_stage.reserve(total));
     }
-    double* pin = (double*)d->io_pin;
+    double* pin = (double*)d->io_pin.get();
     for (size_t i = 0; i < total; i++) pin[i] = src_dtype == MJB_F32 ? (double)((const float*)src)[i] : ((const double*)src)[i];
-    HIPCHK(hipMemcpyAsync(d->prm_stage, pin, bytes, hipMemcpyHostToDevice, d->stream));
-    from = d->prm_stage; from_f32 = 0;
+    HIPCHK(hipMemcpyAsync(d->prm_stage.get(), pin, bytes, hipMemcpyHostToDevice, d->stream));
+    from = d->prm_stage.get(); from_f32 = 0;
   }
   const int threads = 256;
   hipLaunchKernelGGL(k_prm_set, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, d->stream, from, from_f32, n, d->batch,
-                     env_mask, d->prm_d[k], d->prm_f[k]);
+                     env_mask, d->prm_d[k].get(), d->prm_f[k].get());
   HIPCHK(hipGetLastError());
   if (k == PRM_BODY_MASS)
-    hipLaunchKernelGGL(k_prm_subtreemass, dim3((unsigned)((d->batch + 63) / 64)), dim3(64), 0, d->stream, d->prm_d[k], d->md.body_parentid, h.nbody,
-                       d->batch, env_mask, d->prm_d[PRM_SUBTREEMASS], d->prm_f[PRM_SUBTREEMASS]);
+    hipLaunchKernelGGL(k_prm_subtreemass, dim3((unsigned)((d->batch + 63) / 64)), dim3(64), 0, d->stream, d->prm_d[k].get(), d->md.body_parentid, h.nbody,
+                       d->batch, env_mask, d->prm_d[PRM_SUBTREEMASS].get(), d->prm_f[PRM_SUBTREEMASS].get());
   else if (k == PRM_GEOM_FRICTION && h.npair > 0) {
     const size_t np = (size_t)d->batch * h.npair;
-    hipLaunchKernelGGL(k_prm_pair_friction, dim3((unsigned)((np + threads - 1) / threads)), dim3(threads), 0, d->stream, d->prm_d[k], d->md.pair_geom1,
-                       d->md.pair_geom2, h.ngeom, h.npair, d->batch, env_mask, d->prm_d[PRM_PAIR_FRICTION], d->prm_f[PRM_PAIR_FRICTION]);
+    hipLaunchKernelGGL(k_prm_pair_friction, dim3((unsigned)((np + threads - 1) / threads)), dim3(threads), 0, d->stream, d->prm_d[k].get(), d->md.pair_geom1,
+                       d->md.pair_geom2, h.ngeom, h.npair, d->batch, env_mask, d->prm_d[PRM_PAIR_FRICTION].get(), d->prm_f[PRM_PAIR_FRICTION].get());
   }
   HIPCHK(hipGetLastError());
   if (!src_on_device) HIPCHK(hipStreamSynchronize(d->stream));            // the pinned block is free again on return
@@ -1303,7 +1266,7 @@ int mjb_get_env_param(mjbData* d, const char* name, double* host_out) {
   const int k = prm_index(name);
   if (k < 0) return fail(MJB_ERR_ARG, std::string("mjb_get_env_param: unknown per-environment field '") + (name ? name : "") + "'");
   const long n = prm_count(d->model->h, k);
-  if (!d->prm_d[k]) {
+  if (!d->prm_d[k].get()) {
     std::vector<double> v;
     std::string err;
     if (!prm_model_values(d->model, k, v, err)) return fail(MJB_ERR_ARG, err);
@@ -1311,14 +1274,14 @@ int mjb_get_env_param(mjbData* d, const char* name, double* host_out) {
     return MJB_OK;
   }
   HIPCHK(hipSetDevice(d->device));
-  return copy_out(d, ArrayInfo{d->prm_d[k], n, 1}, host_out);
+  return copy_out(d, ArrayInfo{d->prm_d[k].get(), n, 1}, host_out);
 }
 
 int mjb_clear_env_param(mjbData* d, const char* name) {
   if (!d) return fail(MJB_ERR_ARG, "data is NULL");
   const int k = prm_index(name);
   if (k < 0) return fail(MJB_ERR_ARG, std::string("mjb_clear_env_param: unknown per-environment field '") + (name ? name : "") + "'");
-  if (!d->prm_d[k]) return MJB_OK;
+  if (!d->prm_d[k].get()) return MJB_OK;
   HIPCHK(hipSetDevice(d->device));
   HIPCHK(hipStreamSynchronize(d->stream));                     // launches already queued read these rows
   prm_free(d, k);
@@ -1342,13 +1305,16 @@ int mjb_set_feedback(mjbData* d, const double* K, const double* u0, const double
   const size_t n[4] = {(size_t)h.nu * 2 * h.nv, (size_t)h.nu, (size_t)h.nq, (size_t)h.nv};
   const double* src[4] = {K, u0, q0, v0};
   for (int k = 0; k < 4; k++) {
-    if (!d->fbd[k] && (dev_alloc(d, &d->fbd[k], n[k]) || dev_alloc(d, &d->fbf[k], n[k]))) return fail(MJB_ERR_DEVICE, "device allocation of feedback gains failed");
+    if (reserve_zeroed(d->fbd[k], n[k] ? n[k] : 1) != hipSuccess || reserve_zeroed(d->fbf[k], n[k] ? n[k] : 1) != hipSuccess) {
+      for (int j = 0; j < 4; j++) reset_all(d->fbd[j], d->fbf[j]);   // all eight blocks or none (an empty array still gets one element)
+      return fail(MJB_ERR_DEVICE, "device allocation of feedback gains failed");
+    }
     std::vector<double> vd(n[k], 0.0);
     if (src[k]) vd.assign(src[k], src[k] + n[k]);
     std::vector<float> vf(vd.begin(), vd.end());
     if (n[k]) {
-      HIPCHK(hipMemcpy(d->fbd[k], vd.data(), n[k] * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d->fbf[k], vf.data(), n[k] * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d->fbd[k].get(), vd.data(), n[k] * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d->fbf[k].get(), vf.data(), n[k] * sizeof(float), hipMemcpyHostToDevice));
     }
   }
   return MJB_OK;
@@ -1364,13 +1330,16 @@ int mjb_set_feedback_noise(mjbData* d, const double* noise_std, const double* no
   HIPCHK(hipStreamSynchronize(d->stream));
   const size_t n[2] = {(size_t)h.nu, (size_t)nsteps * h.nu};
   const double* src[2] = {noise_std, noise_table};
+  d->fb_nsteps = 0;                                            // until the new table is complete
   for (int k = 0; k < 2; k++) {
-    double* pd = nullptr; float* pf = nullptr;
-    if (dev_alloc(d, &pd, n[k]) || dev_alloc(d, &pf, n[k])) return fail(MJB_ERR_DEVICE, "device allocation of the feedback noise failed");
+    // the previous table's blocks are reused when large enough, else replaced (the stream has drained: no kernel still reads them)
+    if (d->fb_noise_d[k].reserve(n[k] ? n[k] : 1) != hipSuccess || d->fb_noise_f[k].reserve(n[k] ? n[k] : 1) != hipSuccess) {
+      reset_all(d->fb_noise_d[0], d->fb_noise_f[0], d->fb_noise_d[1], d->fb_noise_f[1]);
+      return fail(MJB_ERR_DEVICE, "device allocation of the feedback noise failed");
+    }
     std::vector<float> vf(src[k], src[k] + n[k]);
-    HIPCHK(hipMemcpy(pd, src[k], n[k] * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pf, vf.data(), n[k] * sizeof(float), hipMemcpyHostToDevice));
-    d->fb_noise_d[k] = pd; d->fb_noise_f[k] = pf;             // earlier tables stay owned by the data object until it is freed
+    HIPCHK(hipMemcpy(d->fb_noise_d[k].get(), src[k], n[k] * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->fb_noise_f[k].get(), vf.data(), n[k] * sizeof(float), hipMemcpyHostToDevice));
   }
   d->fb_nsteps = nsteps;
   return MJB_OK;
@@ -1378,7 +1347,7 @@ int mjb_set_feedback_noise(mjbData* d, const double* noise_std, const double* no
 
 int mjb_feedback_ctrl(mjbData* d, int step) {
   if (!d) return fail(MJB_ERR_ARG, "data is NULL");
-  if (!d->fbd[0]) return fail(MJB_ERR_ARG, "mjb_feedback_ctrl needs mjb_set_feedback() first");
+  if (!d->fbd[0].get()) return fail(MJB_ERR_ARG, "mjb_feedback_ctrl needs mjb_set_feedback() first");
   const HostModel& h = d->model->h;
   if (h.nu == 0) return MJB_OK;
   HIPCHK(hipSetDevice(d->device));
@@ -1387,17 +1356,17 @@ int mjb_feedback_ctrl(mjbData* d, int step) {
   std::memset(&a, 0, sizeof(a));
   a.nsteps = d->fb_nsteps; a.step = step; a.env_stride = d->fb_env_stride;
   if (d->dtype == MJB_F32) {
-    a.K = d->fbf[0]; a.u0 = d->fbf[1]; a.q0 = d->fbf[2]; a.v0 = d->fbf[3];
-    if (d->fb_nsteps > 0) { a.noise_std = d->fb_noise_f[0]; a.noise_tab = d->fb_noise_f[1]; }
+    a.K = d->fbf[0].get(); a.u0 = d->fbf[1].get(); a.q0 = d->fbf[2].get(); a.v0 = d->fbf[3].get();
+    if (d->fb_nsteps > 0) { a.noise_std = d->fb_noise_f[0].get(); a.noise_tab = d->fb_noise_f[1].get(); }
     const int kpad = (2 * h.nv + 1) & ~1;
     const size_t shmem = (size_t)32 * kpad * sizeof(float);
     if (shmem > 64 * 1024) return fail(MJB_ERR_ARG, "mjb_feedback_ctrl: 2 nv too large for the LDS tile");
     hipLaunchKernelGGL(k_feedback_mfma<0>, dim3((unsigned)((d->batch + 31) / 32)), dim3(64), shmem, d->stream, (const DevModel<float>*)d->mf_dev, d->df, a);
   } else {
-    a.K = d->fbd[0]; a.u0 = d->fbd[1]; a.q0 = d->fbd[2]; a.v0 = d->fbd[3];
-    if (d->fb_nsteps > 0) { a.noise_std = d->fb_noise_d[0]; a.noise_tab = d->fb_noise_d[1]; }
-    if (!d->fb_dx && dev_alloc(d, &d->fb_dx, (size_t)d->batch * 2 * h.nv)) return fail(MJB_ERR_DEVICE, "device allocation of the feedback scratch failed");
-    hipLaunchKernelGGL(k_feedback_simple<double>, dim3((unsigned)d->batch), dim3(64), 0, d->stream, (const DevModel<double>*)d->md_dev, d->dd, a, d->fb_dx);
+    a.K = d->fbd[0].get(); a.u0 = d->fbd[1].get(); a.q0 = d->fbd[2].get(); a.v0 = d->fbd[3].get();
+    if (d->fb_nsteps > 0) { a.noise_std = d->fb_noise_d[0].get(); a.noise_tab = d->fb_noise_d[1].get(); }
+    if (reserve_zeroed(d->fb_dx, (size_t)d->batch * 2 * h.nv) != hipSuccess) return fail(MJB_ERR_DEVICE, "device allocation of the feedback scratch failed");
+    hipLaunchKernelGGL(k_feedback_simple<double>, dim3((unsigned)d->batch), dim3(64), 0, d->stream, (const DevModel<double>*)d->md_dev, d->dd, a, d->fb_dx.get());
   }
   HIPCHK(hipGetLastError());
   return MJB_OK;
@@ -1415,14 +1384,13 @@ int mjb_obs_spec_create(mjbData* d, int flags, int nsite, const int* site_ids, i
   mjbObsSpec* s = new mjbObsSpec();
   std::memset(&s->dev, 0, sizeof(s->dev));
   auto up = [&](const int* ids, int n) -> const int* {
-    void* p = nullptr;
-    if (hipMalloc(&p, sizeof(int) * (n > 0 ? n : 1)) != hipSuccess) return nullptr;
-    s->owned.push_back(p);
-    if (n > 0) (void)hipMemcpy(p, ids, sizeof(int) * n, hipMemcpyHostToDevice);
-    return (const int*)p;
+    int* p = s->arena.alloc<int>(n > 0 ? n : 0);
+    if (p && n > 0 && hipMemcpy(p, ids, sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) s->arena.ok = false;
+    return p;
   };
   s->dev.flags = flags; s->dev.nsite = nsite; s->dev.nbody = nbody; s->dev.ngeom = ngeom; s->dev.nsubtree = nsubtree;
   s->dev.site_ids = up(site_ids, nsite); s->dev.body_ids = up(body_ids, nbody); s->dev.geom_ids = up(geom_ids, ngeom); s->dev.subtree_ids = up(subtree_ids, nsubtree);
+  if (!s->arena.ok) { delete s; return fail(MJB_ERR_DEVICE, "device upload of the observation id tables failed"); }
   int dim = 3 * (nsite + nbody + ngeom + nsubtree);
   if (flags & 1) dim += h.nq;
   if (flags & 2) dim += h.nv;
@@ -1435,11 +1403,7 @@ int mjb_obs_spec_create(mjbData* d, int flags, int nsite, const int* site_ids, i
   return MJB_OK;
 }
 
-void mjb_obs_spec_free(mjbObsSpec* s) {
-  if (!s) return;
-  for (void* p : s->owned) (void)hipFree(p);
-  delete s;
-}
+void mjb_obs_spec_free(mjbObsSpec* s) { delete s; }
 
 int mjb_obs_dim(const mjbObsSpec* s) { return s ? s->dev.dim : -1; }
 
@@ -1461,19 +1425,14 @@ static const unsigned long long kFdSlabBytes = 128ull << 20;
 
 // fd_y / fd_valid for `npoint` points: allocated once per data object and grown only when a larger slab comes
 static int fd_scratch(mjbData* d, size_t npoint, int ncol) {
-  if (npoint <= d->fd_cap) return MJB_OK;
   const HostModel& h = d->model->h;
-  if (d->fd_y) (void)hipFree(d->fd_y);                           // hipFree waits for the kernels that may still read it
-  if (d->fd_valid) (void)hipFree(d->fd_valid);
-  d->fd_y = nullptr; d->fd_valid = nullptr; d->fd_cap = 0;
-  if (hipMalloc((void**)&d->fd_y, npoint * ncol * (size_t)(h.nq + h.nv) * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&d->fd_valid, npoint * ncol * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    if (d->fd_y) (void)hipFree(d->fd_y);
-    d->fd_y = nullptr; d->fd_valid = nullptr;
+  const size_t ny = npoint * ncol * (size_t)(h.nq + h.nv), nvalid = npoint * ncol;
+  if (ny <= d->fd_y.count() && nvalid <= d->fd_valid.count()) return MJB_OK;
+  // reserve releases the old blocks through hipFree, which waits for the kernels that may still read them
+  if (d->fd_y.reserve(ny) != hipSuccess || d->fd_valid.reserve(nvalid) != hipSuccess) {
+    (void)hipGetLastError(); reset_all(d->fd_y, d->fd_valid);
     return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
   }
-  d->fd_cap = npoint;
   return MJB_OK;
 }
 
@@ -1514,16 +1473,16 @@ static int fd_run_slab(mjbData* d, const FdPoints& pt, double eps, int centered,
     const long ngroups = (long)pt.npoint * njob;
     const DevModel<double>* mg = d->md_dev; const Lay* lg = d->Ld_dev;
     DevData<float> dvf = d->df; DevData<double> dvd = d->dd;
-    int ncol_ = ncol, cv = chunk, cc = chunk; double eps_ = eps; double* yy = d->fd_y; int* vv = d->fd_valid; FdPoints pp = pt;
+    int ncol_ = ncol, cv = chunk, cc = chunk; double eps_ = eps; double* yy = d->fd_y.get(); int* vv = d->fd_valid.get(); FdPoints pp = pt;
     void* args[] = {(void*)&mg, (void*)&lg, d->dtype == MJB_F32 ? (void*)&dvf : (void*)&dvd, (void*)&ncol_, (void*)&eps_, (void*)&yy, (void*)&vv, (void*)&cv, (void*)&cc, (void*)&pp};
     e = hipModuleLaunchKernel(d->spec[MJB_KERNEL_FD].fn, (unsigned)((ngroups + epb - 1) / epb), 1, 1, 64, 1, 1, (unsigned)((size_t)epb * d->cfg.Ld.bytes), d->stream, args, nullptr);
   } else
-  e = d->dtype == MJB_F32 ? launch_fd<double, float>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->df, pt, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream)
-                          : launch_fd<double, double>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, pt, ncol, h.nv, h.nu, chunk, eps, d->fd_y, d->fd_valid, d->stream);
+  e = d->dtype == MJB_F32 ? launch_fd<double, float>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->df, pt, ncol, h.nv, h.nu, chunk, eps, d->fd_y.get(), d->fd_valid.get(), d->stream)
+                          : launch_fd<double, double>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, pt, ncol, h.nv, h.nu, chunk, eps, d->fd_y.get(), d->fd_valid.get(), d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("fd launch: ") + hipGetErrorString(e));
   const long nthreads = (long)pt.npoint * nin;
   hipLaunchKernelGGL(k_fd_combine<double>, dim3((unsigned)((nthreads + 127) / 128)), dim3(128), 0, d->stream, (const DevModel<double>*)d->md_dev, pt.npoint, ncol, centered, eps,
-                     (const double*)d->fd_y, (const int*)d->fd_valid, A, B);
+                     (const double*)d->fd_y.get(), (const int*)d->fd_valid.get(), A, B);
   HIPCHK(hipGetLastError());
   return MJB_OK;
 }
@@ -1536,11 +1495,11 @@ static int transition_fd_impl(mjbData* d, double eps, int centered) {
   { int rc0 = refresh_options(d); if (rc0 != MJB_OK) return rc0; }
   const int nx = 2 * h.nv;
   size_t B = (size_t)d->batch;
-  if (!d->fd_A) {
-    if (dev_alloc(d, &d->fd_A, B * nx * nx) || dev_alloc(d, &d->fd_B, B * nx * (h.nu > 0 ? h.nu : 1)))
-      return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
-    HIPCHK(hipHostMalloc((void**)&d->fd_A_host, B * nx * nx * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&d->fd_B_host, B * nx * (h.nu > 0 ? h.nu : 1) * sizeof(double), hipHostMallocDefault));
+  const size_t nA = B * nx * nx, nB = B * nx * (h.nu > 0 ? h.nu : 1);
+  if (reserve_zeroed(d->fd_A, nA) != hipSuccess || reserve_zeroed(d->fd_B, nB) != hipSuccess ||          // the four result blocks together
+      d->fd_A_host.reserve(nA) != hipSuccess || d->fd_B_host.reserve(nB) != hipSuccess) {
+    reset_all(d->fd_A, d->fd_B, d->fd_A_host, d->fd_B_host);
+    return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
   }
   // the point table of T = 1 over the data's own arrays: point e = environment e, one slab
   FdPoints pt;
@@ -1553,10 +1512,10 @@ static int transition_fd_impl(mjbData* d, double eps, int centered) {
   // into the pinned result blocks (device-visible) - no staging copies; larger batches keep the device blocks + one async copy each
   const bool zero_copy = B * nx * (nx + (size_t)h.nu) * sizeof(double) <= (size_t)256 * 1024;
   { int rc = fd_order_begin(d); if (rc != MJB_OK) return rc; }
-  { int rc = fd_run_slab(d, pt, eps, centered, zero_copy ? d->fd_A_host : d->fd_A, zero_copy ? d->fd_B_host : d->fd_B); if (rc != MJB_OK) return rc; }
+  { int rc = fd_run_slab(d, pt, eps, centered, zero_copy ? d->fd_A_host.get() : d->fd_A.get(), zero_copy ? d->fd_B_host.get() : d->fd_B.get()); if (rc != MJB_OK) return rc; }
   if (!zero_copy) {
-    HIPCHK(hipMemcpyAsync(d->fd_A_host, d->fd_A, B * nx * nx * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if (h.nu > 0) HIPCHK(hipMemcpyAsync(d->fd_B_host, d->fd_B, B * nx * h.nu * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(d->fd_A_host.get(), d->fd_A.get(), B * nx * nx * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if (h.nu > 0) HIPCHK(hipMemcpyAsync(d->fd_B_host.get(), d->fd_B.get(), B * nx * h.nu * sizeof(double), hipMemcpyDeviceToHost, d->stream));
   }
   HIPCHK(hipStreamSynchronize(d->stream));
   d->fd_pending = false;                                       // this stream has drained, and every earlier FD launch was ordered before it
@@ -1852,8 +1811,8 @@ int mjb_transition_fd(mjbData* d, double eps, int centered, double* A_host, doub
   if (rc != MJB_OK) return rc;
   const HostModel& h = d->model->h;
   const size_t B = (size_t)d->batch, nx = 2 * (size_t)h.nv;
-  std::memcpy(A_host, d->fd_A_host, B * nx * nx * sizeof(double));
-  if (h.nu > 0) std::memcpy(B_host, d->fd_B_host, B * nx * h.nu * sizeof(double));
+  std::memcpy(A_host, d->fd_A_host.get(), B * nx * nx * sizeof(double));
+  if (h.nu > 0) std::memcpy(B_host, d->fd_B_host.get(), B * nx * h.nu * sizeof(double));
   return MJB_OK;
 }
 
@@ -1861,7 +1820,7 @@ int mjb_transition_fd_pinned(mjbData* d, double eps, int centered, const double*
   if (!d || !A_pinned || !B_pinned) return fail(MJB_ERR_ARG, "NULL argument");
   int rc = transition_fd_impl(d, eps, centered);
   if (rc != MJB_OK) return rc;
-  *A_pinned = d->fd_A_host; *B_pinned = d->fd_B_host;
+  *A_pinned = d->fd_A_host.get(); *B_pinned = d->fd_B_host.get();
   return MJB_OK;
 }
 
@@ -1881,40 +1840,28 @@ int mjb_jac(mjbData* d, int nreq, const int* kinds, const int* ids, double* jacp
   if (n == 0) return MJB_OK;
   // persistent buffers instead of four hipMalloc / hipFree and four blocking copies per call (a controller with needs_jacobians calls this
   // once per Env.step): request in pinned memory read by the kernel, results pinned, device staging only for large requests
-  if (nreq > d->jac_req_cap) {
-    if (d->jac_req_pin) (void)hipHostFree(d->jac_req_pin);
-    d->jac_req_pin = nullptr; d->jac_req_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&d->jac_req_pin, sizeof(int) * 2 * (size_t)nreq, hipHostMallocDefault));
-    d->jac_req_cap = nreq;
-  }
-  if (n > d->jac_pin_cap) {
-    for (int k = 0; k < 2; k++) { if (d->jac_pin[k]) (void)hipHostFree(d->jac_pin[k]); d->jac_pin[k] = nullptr; }
-    d->jac_pin_cap = 0;
-    for (int k = 0; k < 2; k++) HIPCHK(hipHostMalloc((void**)&d->jac_pin[k], sizeof(double) * n, hipHostMallocDefault));
-    d->jac_pin_cap = n;
-  }
+  HIPCHK(d->jac_req_pin.reserve(2 * (size_t)nreq));
   const bool zero_copy = 2 * n * sizeof(double) <= (size_t)256 * 1024;
-  if (!zero_copy && n > d->jac_dev_cap) {
-    for (int k = 0; k < 2; k++) { if (d->jac_dev[k]) (void)hipFree(d->jac_dev[k]); d->jac_dev[k] = nullptr; }
-    d->jac_dev_cap = 0;
-    for (int k = 0; k < 2; k++) HIPCHK(hipMalloc((void**)&d->jac_dev[k], sizeof(double) * n));
-    d->jac_dev_cap = n;
+  if (d->jac_pin[0].reserve(n) != hipSuccess || d->jac_pin[1].reserve(n) != hipSuccess ||            // each pair to exactly n
+      (!zero_copy && (d->jac_dev[0].reserve(n) != hipSuccess || d->jac_dev[1].reserve(n) != hipSuccess))) {
+    reset_all(d->jac_pin[0], d->jac_pin[1], d->jac_dev[0], d->jac_dev[1]);
+    return fail(MJB_ERR_DEVICE, "mjb_jac: allocation of the result blocks failed");
   }
   HIPCHK(hipStreamSynchronize(d->stream));                       // nothing queued may still be reading the previous request
-  std::memcpy(d->jac_req_pin, kinds, sizeof(int) * nreq);
-  std::memcpy(d->jac_req_pin + nreq, ids, sizeof(int) * nreq);
-  double *op = zero_copy ? d->jac_pin[0] : d->jac_dev[0], *orr = zero_copy ? d->jac_pin[1] : d->jac_dev[1];
-  const int *dk = d->jac_req_pin, *di = d->jac_req_pin + nreq;
+  std::memcpy(d->jac_req_pin.get(), kinds, sizeof(int) * nreq);
+  std::memcpy(d->jac_req_pin.get() + nreq, ids, sizeof(int) * nreq);
+  double *op = zero_copy ? d->jac_pin[0].get() : d->jac_dev[0].get(), *orr = zero_copy ? d->jac_pin[1].get() : d->jac_dev[1].get();
+  const int *dk = d->jac_req_pin.get(), *di = d->jac_req_pin.get() + nreq;
   hipError_t e = d->dtype == MJB_F32 ? launch_jac<double, float>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->df, nreq, dk, di, op, orr, d->stream)
                                      : launch_jac<double, double>(d->cfg.G_fd, d->md_dev, d->Ld_dev, d->cfg.Ld, d->dd, nreq, dk, di, op, orr, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("jac launch: ") + hipGetErrorString(e));
   if (!zero_copy) {
-    HIPCHK(hipMemcpyAsync(d->jac_pin[0], d->jac_dev[0], n * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    if (jacr_host) HIPCHK(hipMemcpyAsync(d->jac_pin[1], d->jac_dev[1], n * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(d->jac_pin[0].get(), d->jac_dev[0].get(), n * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if (jacr_host) HIPCHK(hipMemcpyAsync(d->jac_pin[1].get(), d->jac_dev[1].get(), n * sizeof(double), hipMemcpyDeviceToHost, d->stream));
   }
   if (hipStreamSynchronize(d->stream) != hipSuccess) return fail(MJB_ERR_DEVICE, "jac sync failed");
-  std::memcpy(jacp_host, d->jac_pin[0], n * sizeof(double));
-  if (jacr_host) std::memcpy(jacr_host, d->jac_pin[1], n * sizeof(double));
+  std::memcpy(jacp_host, d->jac_pin[0].get(), n * sizeof(double));
+  if (jacr_host) std::memcpy(jacr_host, d->jac_pin[1].get(), n * sizeof(double));
   return MJB_OK;
 }
 
@@ -2056,7 +2003,7 @@ int mjb_differentiate_pos(const mjbModel* m, int batch, double* qvel_out, double
 // host mirror: ONE pinned float64 block per data object, one pack kernel + ONE copy per direction
 // ---------------------------------------------------------------------------------------------------------------------
 static int ensure_mirror(mjbData* d) {
-  if (d->mirror_host) return MJB_OK;
+  if (d->mirror_host.get() && d->mirror_dev.get()) return MJB_OK;
   const HostModel& h = d->model->h;
   const size_t B = (size_t)d->batch, n[6] = {(size_t)h.nq, (size_t)h.nv, (size_t)h.nu, (size_t)h.nv, (size_t)h.nv, 1};
   size_t o = 0;
@@ -2065,9 +2012,10 @@ static int ensure_mirror(mjbData* d) {
   HIPCHK(hipSetDevice(d->device));
   // + the engine-flags word + one completion word per environment (polled by mjb_step_host on the zero-copy path: coherent memory, the
   // device's stores must be visible to the host while the kernel is still running)
-  HIPCHK(hipHostMalloc((void**)&d->mirror_host, (o + 1 + B) * sizeof(double), hipHostMallocCoherent));
-  std::memset(d->mirror_host, 0, (o + 1 + B) * sizeof(double));
-  if (dev_alloc(d, &d->mirror_dev, o + 1)) return fail(MJB_ERR_DEVICE, "device allocation of the mirror staging block failed");
+  if (reserve_zeroed(d->mirror_host, o + 1 + B) != hipSuccess || reserve_zeroed(d->mirror_dev, o + 1) != hipSuccess) {   // both or neither
+    reset_all(d->mirror_host, d->mirror_dev);
+    return fail(MJB_ERR_DEVICE, "device allocation of the mirror staging block failed");
+  }
   return MJB_OK;
 }
 static const char* const kMirrorNames[6] = {"qpos", "qvel", "ctrl", "qacc", "qacc_warmstart", "time"};
@@ -2078,9 +2026,9 @@ int mjb_host_view(mjbData* d, const char* name, double** host_ptr, long* per_env
   if (rc != MJB_OK) return rc;
   const HostModel& h = d->model->h;
   const long n[6] = {h.nq, h.nv, h.nu, h.nv, h.nv, 1};
-  if (!std::strcmp(name, "engine_flags")) { *host_ptr = d->mirror_host + d->mirror_off[6]; if (per_env) *per_env = 0; return MJB_OK; }
+  if (!std::strcmp(name, "engine_flags")) { *host_ptr = d->mirror_host.get() + d->mirror_off[6]; if (per_env) *per_env = 0; return MJB_OK; }
   for (int k = 0; k < 6; k++) if (!std::strcmp(name, kMirrorNames[k])) {
-    *host_ptr = d->mirror_host + d->mirror_off[k];
+    *host_ptr = d->mirror_host.get() + d->mirror_off[k];
     if (per_env) *per_env = n[k];
     return MJB_OK;
   }
@@ -2095,11 +2043,11 @@ static int mirror_pull(mjbData* d) {
   const HostModel& h = d->model->h;
   const long total = (long)d->mirror_off[6];
   const unsigned grid = (unsigned)((total + 255) / 256);
-  double* dst = mirror_zero_copy(d) ? d->mirror_host : d->mirror_dev;
+  double* dst = mirror_zero_copy(d) ? d->mirror_host.get() : d->mirror_dev.get();
   if (d->dtype == MJB_F32) hipLaunchKernelGGL(k_mirror_pack<float>, dim3(grid), dim3(256), 0, d->stream, d->df, h.nq, h.nv, h.nu, dst, total);
   else hipLaunchKernelGGL(k_mirror_pack<double>, dim3(grid), dim3(256), 0, d->stream, d->dd, h.nq, h.nv, h.nu, dst, total);
   HIPCHK(hipGetLastError());
-  if (dst == d->mirror_dev) HIPCHK(hipMemcpyAsync(d->mirror_host, d->mirror_dev, (size_t)(total + 1) * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+  if (dst == d->mirror_dev.get()) HIPCHK(hipMemcpyAsync(d->mirror_host.get(), d->mirror_dev.get(), (size_t)(total + 1) * sizeof(double), hipMemcpyDeviceToHost, d->stream));
   HIPCHK(hipStreamSynchronize(d->stream));
   return engine_check(d);
 }
@@ -2112,8 +2060,8 @@ static int mirror_push(mjbData* d, int mask) {
   while (!((mask >> lo) & 1)) lo++;
   while (!((mask >> hi) & 1)) hi--;
   const size_t a = d->mirror_off[lo], b = d->mirror_off[hi + 1];       // one contiguous span covering the edited fields
-  const double* src = mirror_zero_copy(d) ? d->mirror_host : d->mirror_dev;
-  if (src == d->mirror_dev) HIPCHK(hipMemcpyAsync(d->mirror_dev + a, d->mirror_host + a, (b - a) * sizeof(double), hipMemcpyHostToDevice, d->stream));
+  const double* src = mirror_zero_copy(d) ? d->mirror_host.get() : d->mirror_dev.get();
+  if (src == d->mirror_dev.get()) HIPCHK(hipMemcpyAsync(d->mirror_dev.get() + a, d->mirror_host.get() + a, (b - a) * sizeof(double), hipMemcpyHostToDevice, d->stream));
   const long total = (long)d->mirror_off[6];
   const unsigned grid = (unsigned)((total + 255) / 256);
   if (d->dtype == MJB_F32) hipLaunchKernelGGL(k_mirror_unpack<float>, dim3(grid), dim3(256), 0, d->stream, d->df, h.nq, h.nv, h.nu, src, total, mask);
@@ -2148,8 +2096,8 @@ int mjb_step_host(mjbData* d, int nstep, int field_mask) {
   if (nstep > 0 && mirror_zero_copy(d) && d->dtype == MJB_F32) {
     // small batches: ONE launch - the step kernel reads the edited fields from the pinned block and writes the new state back into it
     StepArgs a = make_args(d, nstep, MJB_CTRL_KEEP, 0, 0, 1.0, 0);
-    a.mirror = d->mirror_host; a.mirror_mask = field_mask & 63;
-    double* flagword = d->mirror_host + d->mirror_off[6];
+    a.mirror = d->mirror_host.get(); a.mirror_mask = field_mask & 63;
+    double* flagword = d->mirror_host.get() + d->mirror_off[6];
     // short launches: poll the environments' completion words in the pinned block instead of waiting for the end-of-kernel signal
     // (the state words are published before them; whatever else the kernel's epilogue writes is ordered by the stream for later calls)
     static const bool poll_ok = !(std::getenv("MJB_HOST_POLL") && std::atoi(std::getenv("MJB_HOST_POLL")) == 0);
@@ -2187,11 +2135,7 @@ int mjb_step_host(mjbData* d, int nstep, int field_mask) {
 static int ensure_shadow(mjbData* d) {
   int rc = ensure_mirror(d);
   if (rc != MJB_OK) return rc;
-  if (!d->mirror_shadow) {
-    d->mirror_shadow = (double*)std::malloc(d->mirror_off[6] * sizeof(double));
-    if (!d->mirror_shadow) return fail(MJB_ERR_ARG, "out of host memory for the mirror shadow");
-    std::memcpy(d->mirror_shadow, d->mirror_host, d->mirror_off[6] * sizeof(double));
-  }
+  if (d->mirror_shadow.empty()) d->mirror_shadow.assign(d->mirror_host.get(), d->mirror_host.get() + d->mirror_off[6]);
   return MJB_OK;
 }
 
@@ -2202,7 +2146,7 @@ int mjb_mirror_edited_mask(mjbData* d, int* mask_out) {
   int mask = 0;
   for (int k = 0; k < 6; k++) {
     const size_t a = d->mirror_off[k], b = d->mirror_off[k + 1];
-    if (b > a && std::memcmp(d->mirror_host + a, d->mirror_shadow + a, (b - a) * sizeof(double)) != 0) mask |= 1 << k;   // bitwise: -0.0 / NaN payload edits count
+    if (b > a && std::memcmp(d->mirror_host.get() + a, d->mirror_shadow.data() + a, (b - a) * sizeof(double)) != 0) mask |= 1 << k;   // bitwise: -0.0 / NaN payload edits count
   }
   *mask_out = mask;
   return MJB_OK;
@@ -2214,7 +2158,7 @@ int mjb_mirror_commit(mjbData* d, int field_mask) {
   if (rc != MJB_OK) return rc;
   for (int k = 0; k < 6; k++) if ((field_mask >> k) & 1) {
     const size_t a = d->mirror_off[k], b = d->mirror_off[k + 1];
-    std::memcpy(d->mirror_shadow + a, d->mirror_host + a, (b - a) * sizeof(double));
+    std::memcpy(d->mirror_shadow.data() + a, d->mirror_host.get() + a, (b - a) * sizeof(double));
   }
   return MJB_OK;
 }
