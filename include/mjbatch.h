@@ -387,6 +387,42 @@ int mjb_lqr_candidates(mjbData* d, const mjbLqrCandidates* p);
  * above alone: a diagnostic that pins the operand and result fragment maps of v_mfma_f64_16x16x4_f64 with exact integer data. */
 int mjb_lqr_gemm_tn(mjbData* d, int M, int N, int K, const double* a, const double* b, double* c);
 
+/* ---- infinite-horizon LQR design for a batch of systems: the stabilising solution X of the discrete algebraic Riccati equation
+ *   A' X A - X - A' X B (R + B' X B)^-1 B' X A + Q = 0     and the gain     K = (R + B' X B)^-1 B' X A.
+ * The reference designs each of its controllers this way, one system at a time on the host, with scipy.linalg.solve_discrete_are
+ * (examples/humanoid/controllers/lqr.py:114, examples/drone/controllers/lqr.py:358-369); with per-environment model parameters every
+ * environment has its own (A, B) (mjb_transition_fd_points), and this call designs all of them on the device.
+ * The structure-preserving doubling algorithm, per problem e in float64 (iteration k holds 2^k steps of the Riccati recursion):
+ *   R = L L' (Cholesky),  G_0 = sym(B R^-1 B'),  H_0 = Q,  A_0 = A
+ *   repeat k = 0, 1, ...:
+ *     W = I + G_k H_k;  LU of W with partial pivoting, the pivot row the LOWEST index among the rows of largest |.|
+ *     X_A = W^-1 A_k,  X_G = W^-1 G_k
+ *     H_{k+1} = sym(H_k + A_k' (H_k X_A)),  G_{k+1} = sym(G_k + A_k X_G A_k'),  A_{k+1} = A_k X_A
+ *     change = max|H_{k+1} - H_k| / max|H_{k+1}|
+ *   until change <= tol or k + 1 == max_iter        (on change alone, never on stagnation: change may rise before it collapses)
+ *   X = H (bitwise symmetric),  K = (R + B' X B)^-1 B' X A (Cholesky).
+ * SIGN: K is the gain of the reference and of mjb_set_feedback (u = u0 - K dx) - the NEGATIVE of the K of mjb_lqr_backward.
+ * Q [nx, nx] and R [nu, nu] are taken as symmetric and not checked: only their LOWER triangles are read.  No cross term N.
+ * A [nx, nx], B [nx, nu], Q, R per problem e at ptr + e * env_stride (step_stride ignored; env_stride 0 = shared by all problems).
+ * Outputs, dense: X [batch, nx, nx], K [batch, nu, nx], iters [batch] int32, status [batch] int32, change [batch] (NULL = not wanted).
+ * status[e]: 0 converged; 1 a Cholesky pivot of R or of R + B' X B was <= 0 or not finite; 2 an LU pivot was zero or not finite, or
+ * an iterate was not finite (a system that is not stabilisable ends this way); 3 max_iter iterations without change <= tol.  For a
+ * non-zero status X[e] and K[e] are written as ZEROS, iters[e] and change[e] hold what was reached (change = +inf when not finite),
+ * and no other problem is affected.  A problem's results are bitwise the same at any position of any batch.
+ * 1 <= max_iter <= 64 and tol >= 0: the kernel ends in bounded time on any input.  `batch` is this call's, not the data object's.
+ * Checks (before anything is launched: MJB_ERR_ARG with a message, outputs untouched), launch and stream as mjb_lqr_backward: sizes,
+ * tol, max_iter, strides >= 0, required pointers, device memory of the data's device, the highest element inside its allocation; ONE
+ * kernel launch on the data's stream (one workgroup per problem, everything resident in LDS), no scratch memory, no host copy, no
+ * synchronisation. */
+typedef struct mjbLqrDare {
+  int batch, nx, nu, max_iter;
+  double tol;
+  mjbStrided A, B, Q, R;
+  double *X, *K, *change;
+  int *iters, *status;
+} mjbLqrDare;
+int mjb_lqr_dare(mjbData* d, const mjbLqrDare* p);
+
 /* ---- the quadratic trajectory cost, its first-order expansion and the choice among candidates: what an iLQR iteration or a sampling
  * planner needs between mjb_rollout_ctrl / mjb_transition_fd_points and mjb_lqr_backward / mjb_lqr_candidates, on the device.  The
  * reference's humanoid controller builds its Q in the 2nv tangent space (examples/humanoid/controllers/lqr.py:97-114) and takes the

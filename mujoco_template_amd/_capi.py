@@ -61,6 +61,13 @@ class LqrCandidatesStruct(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("alphas", "lo", "hi", "cand")]
 
 
+class LqrDareStruct(ctypes.Structure):
+    """``mjbLqrDare`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("batch", "nx", "nu", "max_iter")] + [("tol", ctypes.c_double)] + \
+               [(n, Strided) for n in ("A", "B", "Q", "R")] + \
+               [(n, ctypes.c_void_p) for n in ("X", "K", "change", "iters", "status")]
+
+
 class StridedIn(ctypes.Structure):
     """``mjbStridedIn``: an ``mjbStrided`` array of float32 (dtype 0) or float64 (dtype 1) elements."""
     _fields_ = [("ptr", ctypes.c_void_p), ("step_stride", ctypes.c_long), ("env_stride", ctypes.c_long), ("dtype", ctypes.c_int)]
@@ -156,6 +163,8 @@ def load_library() -> ctypes.CDLL:
     L.mjb_lqr_backward_box.restype = ci
     L.mjb_lqr_candidates.argtypes = [vp, ctypes.POINTER(LqrCandidatesStruct)]
     L.mjb_lqr_candidates.restype = ci
+    L.mjb_lqr_dare.argtypes = [vp, ctypes.POINTER(LqrDareStruct)]
+    L.mjb_lqr_dare.restype = ci
     L.mjb_lqr_gemm_tn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.mjb_lqr_gemm_tn.restype = ci
     L.mjb_traj_cost.argtypes = [vp, ctypes.POINTER(TrajCostStruct)]
@@ -1051,6 +1060,14 @@ class BatchSim:
     def lqr_candidates(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
         """``mjb_lqr_candidates`` on raw device addresses (see ``lqr_backward``)."""
         self._lqr_call(load_library().mjb_lqr_candidates, LqrCandidatesStruct(), sizes, arrays, pointers, keep)
+
+    def lqr_dare(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_lqr_dare`` on raw device addresses (see ``lqr_backward``): ``sizes`` batch, nx, nu, max_iter, tol; ``arrays`` A, B, Q, R
+        as (address, 0, env stride); ``pointers`` X, K, change (0 = not wanted), iters, status.  ``trajopt.solve_dare`` is the checked
+        tensor interface on top of it."""
+        struct = LqrDareStruct()
+        struct.tol = float(sizes["tol"])
+        self._lqr_call(load_library().mjb_lqr_dare, struct, {k: v for k, v in sizes.items() if k != "tol"}, arrays, pointers, keep)
 
     def traj_cost(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
         """``mjb_traj_cost`` on raw device addresses (see ``lqr_backward``); the state and control entries of ``arrays`` carry a

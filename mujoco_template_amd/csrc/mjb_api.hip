@@ -19,6 +19,7 @@
 #include "mjb_host.hpp"
 #include "mjb_kernels.hpp"
 #include "mjb_lqr.hpp"
+#include "mjb_dare.hpp"
 #include "mjb_traj.hpp"
 
 using namespace mjb;
@@ -1713,6 +1714,35 @@ int mjb_lqr_gemm_tn(mjbData* d, int M, int N, int K, const double* a, const doub
   if ((rc = check_lqr_array(d, fn, "c", c, false, 1, 1, (long)M * N, 0, 0)) != MJB_OK) return rc;
   const hipError_t e = lqr_launch_gemm_probe(M, N, K, a, b, c, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_gemm_tn launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+// ---- mjb_lqr_dare: the checks (those of mjb_lqr_backward); the kernel and its launch are in mjb_dare.hip ----
+int mjb_lqr_dare(mjbData* d, const mjbLqrDare* p) {
+  static const char* fn = "mjb_lqr_dare";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_lqr_dare: NULL argument");
+  static const char* const msg[7] = {"", ": batch must be >= 1", ": nx must lie in [1, 64] (the state the kernel keeps in LDS)", ": nu must lie in [1, 32]",
+                                     ": max_iter must lie in [1, 64]", ": tol must be >= 0", ": batch * nx * nx is too large"};
+  const int why = dare_size_error(p->batch, p->nx, p->nu, p->max_iter, p->tol);
+  if (why) return fail(MJB_ERR_ARG, std::string(fn) + msg[why]);
+  HIPCHK(hipSetDevice(d->device));
+  const long B = p->batch, nx = p->nx, nu = p->nu;
+  int rc;
+  const struct { const char* what; const mjbStrided* s; long n; } in[] = {
+      {"A", &p->A, nx * nx}, {"B", &p->B, nx * nu}, {"Q", &p->Q, nx * nx}, {"R", &p->R, nu * nu}};
+  for (const auto& a : in)
+    if ((rc = check_lqr_array(d, fn, a.what, a.s->ptr, false, 1, B, a.n, 0, a.s->env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "X", p->X, false, 1, B, nx * nx, 0, nx * nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "K", p->K, false, 1, B, nu * nx, 0, nu * nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "change", p->change, true, 1, B, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "iters", p->iters, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "status", p->status, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  DareArgs a;
+  a.B = p->batch; a.nx = p->nx; a.nu = p->nu; a.max_iter = p->max_iter; a.tol = p->tol;
+  a.A = lqr_arr(p->A); a.Bm = lqr_arr(p->B); a.Q = lqr_arr(p->Q); a.R = lqr_arr(p->R);
+  a.X = p->X; a.K = p->K; a.change = p->change; a.iters = p->iters; a.status = p->status;
+  const hipError_t e = dare_launch(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_dare launch: ") + hipGetErrorString(e));
   return MJB_OK;
 }
 

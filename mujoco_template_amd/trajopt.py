@@ -14,7 +14,14 @@ With ``rollout`` and ``linearize_rollout`` these are the phases of an iLQR itera
     select_candidates(data, cc.cost[None], cand, out=u)                        # u <- the best candidate, no host read
 
 The reference designs its controllers from one ``(A, B)`` with ``scipy.linalg.solve_discrete_are``; with ``lx = lu = 0`` the backward
-pass is the finite-horizon, time-varying form of that recursion and ``K[:, t]`` the LQR gain of step ``t``.
+pass is the finite-horizon, time-varying form of that recursion and ``K[:, t]`` the LQR gain of step ``t``.  The equation itself -
+the infinite-horizon design - is ``solve_dare`` (``mjb_lqr_dare``, a doubling algorithm: one launch for every system of a batch), so
+that a per-environment LQR design under domain randomisation never leaves the GPU either::
+
+    data.set_env_params(body_mass=mass)                                          # every environment its own model
+    _, _, A, B = linearize_rollout(model, data, u0[:, None], initial_state=x0)   # T = 1: A [B, 1, nx, nx], B [B, 1, nx, nu]
+    sol = solve_dare(data, A[:, 0], B[:, 0], Q, R)                               # the views are read in place; sol.K [B, nu, nx]
+    # a torch controller on DeviceData: ctrl = u0 - (sol.K @ dx[..., None])[..., 0]   (K has the reference's sign, not lqr_backward's)
 
 Tensors are float64 on the data's GPU, addressed ``[B, T, ...]`` (``time_major=True``: ``[T, B, ...]``) through their own strides:
 the permuted views ``linearize_rollout`` returns, dense tensors of either order and ``expand``-ed ones are read in place.  A tensor of
@@ -233,6 +240,72 @@ def lqr_candidates(data, A, B, k, K, u, alphas, *, dx0=None, lo=None, hi=None, d
     return cand
 
 
+class DareResult(NamedTuple):
+    X: object        # [nb, nx, nx] the stabilising solution of the Riccati equation, bitwise symmetric (zeros where status != 0)
+    K: object        # [nb, nu, nx] the gain of u = u0 - K dx (zeros where status != 0)
+    status: object   # [nb] int32: 0 converged, 1 a Cholesky pivot (R or R + B'XB), 2 an LU pivot or an iterate not finite, 3 max_iter reached
+    iters: object    # [nb] int32 doubling iterations done
+    change: object   # [nb] max|H_{k+1} - H_k| / max|H_{k+1}| of the last iteration (+inf when not finite)
+
+
+def solve_dare(data, A, B, Q, R, *, tol: float = 1e-12, max_iter: int = 32) -> DareResult:
+    """Infinite-horizon LQR design for ``nb`` systems in one kernel launch (``mjb_lqr_dare``): the stabilising solution ``X`` of
+
+        A' X A - X - A' X B (R + B' X B)^-1 B' X A + Q = 0        and        K = (R + B' X B)^-1 B' X A
+
+    - what the reference gets from ``scipy.linalg.solve_discrete_are`` for one system on the host.  The structure-preserving doubling
+    algorithm in float64 (include/mjbatch.h states it): iteration ``k`` holds ``2^k`` steps of the Riccati recursion, so a dozen
+    iterations (19 on the humanoid balance design, whose closed loop keeps marginal modes) reach what ``lqr_backward`` on a constant
+    ``(A, B)`` needs thousands of steps for.  It stops when ``max|H_{k+1} - H_k| / max|H_{k+1}| <= tol`` or after ``max_iter`` (1..64).
+
+    **Sign.**  ``K`` is the gain of the reference and of ``set_feedback`` (``u = u0 - K dx``): the NEGATIVE of ``lqr_backward``'s ``K``.
+
+    ``A [nb, nx, nx]``, ``B [nb, nx, nu]``, ``Q [nb, nx, nx]``, ``R [nb, nu, nu]`` (``nx <= 64``, ``nu <= 32``), float64 on the data's
+    GPU; each may also be its trailing block alone, shared by all problems.  ``nb`` is the leading size of those that have one (they
+    must agree; 1 if none has) and need not be the data's batch.  The leading axis may be strided: the ``A[:, 0]``, ``B[:, 0]`` views
+    of ``linearize_rollout(..., T=1)`` are read in place; a trailing block that is not dense and row-major is copied once with
+    ``.contiguous()``.  ``Q`` and ``R`` are taken as symmetric and not checked: only their lower triangles are read.  No cross term.
+
+    ``status`` (per problem): 0 converged; 1 a Cholesky pivot of ``R`` or ``R + B'XB`` was ``<= 0`` or not finite; 2 an LU pivot was
+    zero or not finite or an iterate was not finite (a system that is not stabilisable ends this way); 3 ``max_iter`` reached.  Where it
+    is not 0, ``X`` and ``K`` are zeros, ``iters`` and ``change`` hold what was reached, and no other problem is affected.  A problem's
+    results are bitwise the same at any position of any batch.  Enqueued on torch's current stream; nothing waits for the GPU and
+    nothing is copied to the host."""
+    import torch
+
+    fn = "solve_dare"
+    sim = _sim(data)
+    dev = torch.device(f"cuda:{sim.device}")
+    for name, x in (("A", A), ("B", B), ("Q", Q), ("R", R)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != dev or x.ndim not in (2, 3):
+            raise ConfigError(f"{fn}: {name} must be a float64 torch tensor [nb, n, m] or [n, m] on {dev}")
+    nx, nu = int(A.shape[-1]), int(B.shape[-1])
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not (tol >= 0):
+        raise ConfigError(f"{fn}: max_iter must be an integer and tol >= 0")
+    lead = {name: int(x.shape[0]) for name, x in (("A", A), ("B", B), ("Q", Q), ("R", R)) if x.ndim == 3}
+    if len(set(lead.values())) > 1:
+        raise ConfigError(f"{fn}: the leading sizes differ: {lead}")
+    nb = next(iter(lead.values())) if lead else 1
+    if nb < 1:
+        raise ConfigError(f"{fn}: at least one problem is required")
+    arrays, keep = {}, []
+    for name, x, trail in (("A", A, (nx, nx)), ("B", B, (nx, nu)), ("Q", Q, (nx, nx)), ("R", R, (nu, nu))):
+        if tuple(x.shape[-2:]) != trail:
+            raise ConfigError(f"{fn}: {name} must have shape {[nb, *trail]} or {list(trail)}, got {list(x.shape)}")
+        if x.numel() and not (x[0] if x.ndim == 3 else x).is_contiguous():     # the trailing block must be dense, row-major
+            x = x.contiguous()
+        es = x.stride(0) if x.ndim == 3 else 0
+        if es < 0:
+            raise ConfigError(f"{fn}: {name} has a negative stride")
+        arrays[name] = (x.data_ptr(), 0, es); keep.append(x)
+    opt = dict(dtype=torch.float64, device=dev)
+    X, K, change = torch.empty((nb, nx, nx), **opt), torch.empty((nb, nu, nx), **opt), torch.empty((nb,), **opt)
+    iters, status = torch.empty((nb,), dtype=torch.int32, device=dev), torch.empty((nb,), dtype=torch.int32, device=dev)
+    sim.lqr_dare({"batch": nb, "nx": nx, "nu": nu, "max_iter": int(max_iter), "tol": float(tol)}, arrays,
+                 {"X": X.data_ptr(), "K": K.data_ptr(), "change": change.data_ptr(), "iters": iters.data_ptr(), "status": status.data_ptr()}, keep=keep)
+    return DareResult(X, K, status, iters, change)
+
+
 class TrajCostResult(NamedTuple):
     cost: object     # [B] float64; +inf where the sum is not finite
     cost_t: object   # [B, T + 1]
@@ -390,4 +463,4 @@ def select_candidates(data, cost, cand, *, mode: str = "argmin", temperature=Non
     return TrajSelectResult(u, best, best_cost, weights)
 
 
-__all__ = ["LqrBackwardResult", "LqrBoxResult", "lqr_backward", "lqr_candidates", "TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]
+__all__ = ["LqrBackwardResult", "LqrBoxResult", "lqr_backward", "lqr_candidates", "DareResult", "solve_dare","TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]

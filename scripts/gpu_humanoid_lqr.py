@@ -80,8 +80,9 @@ def noise_table(model, cfg, bal, duration_s: float):
     return ctrl_std, pert
 
 
-def design(model, cfg=CFG, verbose=True):
-    """Returns dict(qpos0, ctrl0, K, A, B, offset, forces, ctrl_std, perturbations)."""
+def design(model, cfg=CFG, verbose=True, gpu_dare=False):
+    """Returns dict(qpos0, ctrl0, K, A, B, offset, forces, ctrl_std, perturbations).  ``gpu_dare``: K comes from ``mt.solve_dare``
+    (``mjb_lqr_dare``, device tensors in, device tensors out) instead of scipy, and its distance to scipy's K is printed."""
     import scipy.linalg
 
     nv, nu = model.nv, model.nu
@@ -128,6 +129,16 @@ def design(model, cfg=CFG, verbose=True):
     R = np.eye(nu)
     P = scipy.linalg.solve_discrete_are(A, B, Q, R)
     K = np.linalg.solve(R + B.T @ P @ B, B.T @ P @ A)
+    if gpu_dare:
+        import torch
+
+        dev = torch.device(f"cuda:{work.sim.device}")
+        sol = mt.solve_dare(work, *(torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float64, device=dev) for x in (A, B, Q, R)))
+        if int(sol.status[0]) != 0:
+            raise RuntimeError(f"solve_dare: status {int(sol.status[0])} after {int(sol.iters[0])} iterations")
+        K_gpu = sol.K[0].cpu().numpy()
+        print(f"solve_dare: {int(sol.iters[0])} doubling iterations, max|K - K_scipy| / max|K| = {np.abs(K_gpu - K).max() / np.abs(K).max():.3e}")
+        K = K_gpu
     ctrl_std, pert = noise_table(model, cfg, bal, cfg["perturb_duration_s"])
     rho = float(np.abs(np.linalg.eigvals(A - B @ K)).max())
     if verbose:
@@ -200,11 +211,12 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--seconds", type=float, default=12.0)
+    ap.add_argument("--gpu-dare", action="store_true", help="design K on the GPU with mt.solve_dare and print its distance to scipy's")
     args = ap.parse_args()
     model = mj.MjModel.from_xml_path(os.path.join(ROOT, "models/humanoid.xml"))
     print("== DeepMind's tutorial recipe (LQR.txt): balance joints = abdomen + left leg, legacy seed-1 noise over 12 s ==")
     t0 = time.perf_counter()
-    d = design(model, TUTORIAL)
+    d = design(model, TUTORIAL, gpu_dare=args.gpu_dare)
     print(f"design took {time.perf_counter() - t0:.2f} s")
     balance(d, 16, args.seconds, dtype="float64", noise=False)
     print("one humanoid, the tutorial's noise sequence (published behaviour of real MuJoCo: keeps its balance for the 12 s):")
@@ -229,7 +241,7 @@ def main() -> None:
     del e64, e32
     balance(dl, args.batch, args.seconds, dtype="float32", env_stride=stride)
     print("== the reference's variant (lqr.py:218-238: balance joints = every hip / knee / ankle of BOTH legs, the abdomen among the noisy 'other' joints; default_rng(1), 6 s) ==")
-    dr = design(model, CFG)
+    dr = design(model, CFG, gpu_dare=args.gpu_dare)
     u64, u32, dev = single_env_pair(dr, 6.0)
     print(f"  upright after 6 s: float64 {u64}, fp32 {u32}")
 
