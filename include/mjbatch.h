@@ -423,6 +423,43 @@ typedef struct mjbLqrDare {
 } mjbLqrDare;
 int mjb_lqr_dare(mjbData* d, const mjbLqrDare* p);
 
+/* ---- the poles of a batch of (closed-loop) systems: every eigenvalue of M = A + feedback_sign * B K and rho = max |lambda|.
+ * The reference's next line after every design is np.max(np.abs(np.linalg.eigvals(A - B @ K))): it refuses or rescales a gain whose
+ * closed-loop spectral radius is not below 1 (examples/drone/controllers/lqr.py:134-137, examples/drone2/main.py:317-318).  With
+ * per-environment (A, B) this answers on the device which environments a gain stabilises (rho < 1) and by what margin.
+ * SIGN: feedback_sign = -1 is the convention of mjb_lqr_dare and mjb_set_feedback (u = u0 - K dx), +1 that of mjb_lqr_backward.  The
+ * sign is applied to K exactly, so (+1, -K) is bitwise (-1, K).  B.ptr and K.ptr both NULL: M = A (open-loop poles; nu is ignored);
+ * exactly one of them NULL is an error.
+ * The method is LAPACK's for eigenvalues only, per problem e in float64, every iterate resident in LDS, one wavefront per problem:
+ *   1. M = A + s B K on the f64 MFMA.  An entry of M that is not finite (as any such entry of A, B or K makes one) ends with status 1.
+ *   2. if balance != 0: Parlett-Reinsch scaling alone (no permutation), radix 2 and therefore exact: dgebal's loop on the 1-norms of
+ *      the off-diagonal parts of row and column i with its 0.95 acceptance factor, rows in index order until a full pass changes
+ *      nothing, a zero row or column norm leaving that index alone.  scale = D (powers of two); the spectrum computed is that of
+ *      D^-1 M D.  balance == 0: scale is all ones.
+ *   3. Householder reduction to upper Hessenberg form (a reflector of zero norm is the identity).
+ *   4. Francis implicit double-shift QR on the active block alone (dlahqr without Schur vectors): its two-stage small-subdiagonal
+ *      deflation test, exceptional shifts at every 10th and 20th sweep since the last deflation, final 2 x 2 blocks standardised as
+ *      dlanv2 does.  max_sweeps caps the TOTAL number of sweeps of a problem: 0 = LAPACK's 30 * max(10, nx), else 1 .. that number.
+ *   5. the eigenvalues sorted by descending modulus, ties by descending real part, then descending imaginary part.
+ * Inputs: A [nx, nx], B [nx, nu], K [nu, nx] per problem e at ptr + e * env_stride (step_stride ignored; env_stride 0 = shared by all
+ * problems: one K against per-environment A, B is the robustness sweep).  nx <= 64, nu <= 32.
+ * Outputs, dense, all written for every problem: wr, wi [batch, nx] the real and imaginary parts in the order above, a complex pair
+ * as exact conjugates (equal wr, wi bitwise negated, the positive one first); rho [batch] = the modulus of the first, the correctly
+ * rounded sqrt(wr^2 + wi^2); scale [batch, nx]; sweeps [batch] int32 Francis sweeps done; status [batch] int32: 0 ok, 1 an entry not
+ * finite, 2 max_sweeps reached before every eigenvalue had deflated.  For a non-zero status wr[e], wi[e] are NaN and rho[e] is +inf,
+ * so that rho < 1 is false for a failed problem (deliberately not the zeros of mjb_lqr_dare, which would read as stable); no other
+ * problem is affected.  A problem's results are bitwise the same at any position of any batch.
+ * Checks, launch and stream as mjb_lqr_dare (MJB_ERR_ARG with a message before anything is launched, outputs untouched): sizes,
+ * feedback_sign, max_sweeps, strides >= 0, required pointers, device memory of the data's device, the highest element inside its
+ * allocation; ONE kernel launch on the data's stream, no scratch memory, no host copy, no synchronisation. */
+typedef struct mjbLqrEig {
+  int batch, nx, nu, feedback_sign, balance, max_sweeps;
+  mjbStrided A, B, K;
+  double *wr, *wi, *rho, *scale;
+  int *sweeps, *status;
+} mjbLqrEig;
+int mjb_lqr_eig(mjbData* d, const mjbLqrEig* p);
+
 /* ---- the quadratic trajectory cost, its first-order expansion and the choice among candidates: what an iLQR iteration or a sampling
  * planner needs between mjb_rollout_ctrl / mjb_transition_fd_points and mjb_lqr_backward / mjb_lqr_candidates, on the device.  The
  * reference's humanoid controller builds its Q in the 2nv tangent space (examples/humanoid/controllers/lqr.py:97-114) and takes the

@@ -68,6 +68,13 @@ class LqrDareStruct(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("X", "K", "change", "iters", "status")]
 
 
+class LqrEigStruct(ctypes.Structure):
+    """``mjbLqrEig`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("batch", "nx", "nu", "feedback_sign", "balance", "max_sweeps")] + \
+               [(n, Strided) for n in ("A", "B", "K")] + \
+               [(n, ctypes.c_void_p) for n in ("wr", "wi", "rho", "scale", "sweeps", "status")]
+
+
 class StridedIn(ctypes.Structure):
     """``mjbStridedIn``: an ``mjbStrided`` array of float32 (dtype 0) or float64 (dtype 1) elements."""
     _fields_ = [("ptr", ctypes.c_void_p), ("step_stride", ctypes.c_long), ("env_stride", ctypes.c_long), ("dtype", ctypes.c_int)]
@@ -165,6 +172,8 @@ def load_library() -> ctypes.CDLL:
     L.mjb_lqr_candidates.restype = ci
     L.mjb_lqr_dare.argtypes = [vp, ctypes.POINTER(LqrDareStruct)]
     L.mjb_lqr_dare.restype = ci
+    L.mjb_lqr_eig.argtypes = [vp, ctypes.POINTER(LqrEigStruct)]
+    L.mjb_lqr_eig.restype = ci
     L.mjb_lqr_gemm_tn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.mjb_lqr_gemm_tn.restype = ci
     L.mjb_traj_cost.argtypes = [vp, ctypes.POINTER(TrajCostStruct)]
@@ -1068,6 +1077,12 @@ class BatchSim:
         struct = LqrDareStruct()
         struct.tol = float(sizes["tol"])
         self._lqr_call(load_library().mjb_lqr_dare, struct, {k: v for k, v in sizes.items() if k != "tol"}, arrays, pointers, keep)
+
+    def lqr_eig(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_lqr_eig`` on raw device addresses (see ``lqr_backward``): ``sizes`` batch, nx, nu, feedback_sign, balance, max_sweeps
+        (0 = the default cap); ``arrays`` A and, together or not at all, B and K as (address, 0, env stride); ``pointers`` wr, wi, rho,
+        scale, sweeps, status.  ``trajopt.closed_loop_poles`` is the checked tensor interface on top of it."""
+        self._lqr_call(load_library().mjb_lqr_eig, LqrEigStruct(), sizes, arrays, pointers, keep)
 
     def traj_cost(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
         """``mjb_traj_cost`` on raw device addresses (see ``lqr_backward``); the state and control entries of ``arrays`` carry a

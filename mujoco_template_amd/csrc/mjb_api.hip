@@ -20,6 +20,7 @@
 #include "mjb_kernels.hpp"
 #include "mjb_lqr.hpp"
 #include "mjb_dare.hpp"
+#include "mjb_eig.hpp"
 #include "mjb_traj.hpp"
 
 using namespace mjb;
@@ -1743,6 +1744,40 @@ int mjb_lqr_dare(mjbData* d, const mjbLqrDare* p) {
   a.X = p->X; a.K = p->K; a.change = p->change; a.iters = p->iters; a.status = p->status;
   const hipError_t e = dare_launch(a, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_dare launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+// ---- mjb_lqr_eig: the checks (those of mjb_lqr_dare); the kernel and its launch are in mjb_eig.hip ----
+int mjb_lqr_eig(mjbData* d, const mjbLqrEig* p) {
+  static const char* fn = "mjb_lqr_eig";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_lqr_eig: NULL argument");
+  static const char* const msg[7] = {"", ": batch must be >= 1", ": nx must lie in [1, 64] (the matrix the kernel keeps in LDS)", ": nu must lie in [1, 32]",
+                                     ": max_sweeps must be 0 (the default) or lie in [1, 30 * max(10, nx)]", ": feedback_sign must be -1 or +1",
+                                     ": batch * nx * nx is too large"};
+  if ((p->B.ptr == nullptr) != (p->K.ptr == nullptr)) return fail(MJB_ERR_ARG, "mjb_lqr_eig: B and K must be given together (both NULL: the poles of A)");
+  const bool has_bk = p->B.ptr != nullptr;
+  const int why = eig_size_error(p->batch, p->nx, p->nu, has_bk, p->max_sweeps, p->feedback_sign);
+  if (why) return fail(MJB_ERR_ARG, std::string(fn) + msg[why]);
+  HIPCHK(hipSetDevice(d->device));
+  const long B = p->batch, nx = p->nx, nu = has_bk ? p->nu : 0;
+  int rc;
+  if ((rc = check_lqr_array(d, fn, "A", p->A.ptr, false, 1, B, nx * nx, 0, p->A.env_stride)) != MJB_OK) return rc;
+  if (has_bk) {
+    if ((rc = check_lqr_array(d, fn, "B", p->B.ptr, false, 1, B, nx * nu, 0, p->B.env_stride)) != MJB_OK) return rc;
+    if ((rc = check_lqr_array(d, fn, "K", p->K.ptr, false, 1, B, nu * nx, 0, p->K.env_stride)) != MJB_OK) return rc;
+  }
+  if ((rc = check_lqr_array(d, fn, "wr", p->wr, false, 1, B, nx, 0, nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "wi", p->wi, false, 1, B, nx, 0, nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "rho", p->rho, false, 1, B, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "scale", p->scale, false, 1, B, nx, 0, nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "sweeps", p->sweeps, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "status", p->status, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  EigArgs a;
+  a.B = p->batch; a.nx = p->nx; a.nu = (int)nu; a.max_sweeps = p->max_sweeps; a.balance = p->balance ? 1 : 0; a.sign = (double)p->feedback_sign;
+  a.A = lqr_arr(p->A); a.Bm = lqr_arr(p->B); a.K = lqr_arr(p->K);
+  a.wr = p->wr; a.wi = p->wi; a.rho = p->rho; a.scale = p->scale; a.sweeps = p->sweeps; a.status = p->status;
+  const hipError_t e = eig_launch(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_eig launch: ") + hipGetErrorString(e));
   return MJB_OK;
 }
 

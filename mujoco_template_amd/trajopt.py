@@ -23,6 +23,15 @@ that a per-environment LQR design under domain randomisation never leaves the GP
     sol = solve_dare(data, A[:, 0], B[:, 0], Q, R)                               # the views are read in place; sol.K [B, nu, nx]
     # a torch controller on DeviceData: ctrl = u0 - (sol.K @ dx[..., None])[..., 0]   (K has the reference's sign, not lqr_backward's)
 
+The reference's next line after every design is ``np.max(np.abs(np.linalg.eigvals(A - B @ K)))``: it refuses a gain whose closed-loop
+spectral radius is not below 1.  ``closed_loop_poles`` (``mjb_lqr_eig``) is that check for the whole batch in one launch - LAPACK's
+method for eigenvalues alone (power-of-two balancing, Householder reduction to Hessenberg form, Francis double-shift QR with dlahqr's
+deflation tests), one wavefront per system - so the chain is ``... -> solve_dare -> closed_loop_poles -> (rho < 1) mask``::
+
+    poles = closed_loop_poles(data, A[:, 0], B[:, 0], sol.K)                     # wr, wi [B, nx] by descending modulus; rho [B]
+    stable = poles.rho < 1                                                       # False for a failed problem too: its rho is +inf
+    # one nominal gain against every randomised model (K [nu, nx] is read once, no copy): closed_loop_poles(data, A[:, 0], B[:, 0], K_nominal)
+
 Tensors are float64 on the data's GPU, addressed ``[B, T, ...]`` (``time_major=True``: ``[T, B, ...]``) through their own strides:
 the permuted views ``linearize_rollout`` returns, dense tensors of either order and ``expand``-ed ones are read in place.  A tensor of
 the trailing shape alone (``Q [nx, nx]``) is the same for every step and trajectory.  Only the two leading axes may be strided: the
@@ -306,6 +315,86 @@ def solve_dare(data, A, B, Q, R, *, tol: float = 1e-12, max_iter: int = 32) -> D
     return DareResult(X, K, status, iters, change)
 
 
+class PolesResult(NamedTuple):
+    wr: object       # [nb, nx] real parts, by descending modulus, ties by descending wr, then descending wi (NaN where status != 0)
+    wi: object       # [nb, nx] imaginary parts; a complex pair is two neighbours with equal wr and wi bitwise negated, the positive one first
+    rho: object      # [nb] the spectral radius: the correctly rounded sqrt(wr[:, 0]^2 + wi[:, 0]^2) (+inf where status != 0)
+    status: object   # [nb] int32: 0 ok, 1 an entry of A, B, K or M is not finite, 2 max_sweeps reached before every eigenvalue had deflated
+    sweeps: object   # [nb] int32 Francis sweeps done
+    scale: object    # [nb, nx] the balancing diagonal D (powers of two; ones with balance=False): the spectrum computed is that of D^-1 M D
+
+
+def closed_loop_poles(data, A, B=None, K=None, *, feedback_sign: int = -1, balance: bool = True, max_sweeps=None) -> PolesResult:
+    """Every eigenvalue of ``M = A + feedback_sign * B K`` and the spectral radius ``rho = max |lambda|`` for ``nb`` systems in one
+    kernel launch (``mjb_lqr_eig``) - what the reference computes with ``np.max(np.abs(np.linalg.eigvals(A - B @ K)))`` after every
+    design, to refuse a gain that does not stabilise.  ``rho < 1`` is the mask of the stabilised environments.
+
+    **Sign.**  ``feedback_sign=-1`` (the default) is the convention of ``solve_dare`` and ``set_feedback`` (``u = u0 - K dx``); ``+1``
+    is ``lqr_backward``'s.  The sign is applied to ``K`` exactly: ``+1`` with ``-K`` gives the bits of ``-1`` with ``K``.  With ``B``
+    and ``K`` both ``None`` the matrix is ``A`` itself (open-loop poles); exactly one of them is a ``ConfigError``.
+
+    **Method**: LAPACK's for eigenvalues only, in float64, one wavefront per system with the iterate in LDS (include/mjbatch.h states
+    it): ``M`` on the f64 MFMA; with ``balance`` Parlett-Reinsch scaling by powers of two (exact, no permutation; ``scale`` returns the
+    diagonal ``D``, the spectrum computed is that of ``D^-1 M D``); Householder reduction to Hessenberg form; Francis implicit
+    double-shift QR with ``dlahqr``'s deflation tests and exceptional shifts and ``dlanv2``'s 2 x 2 blocks.  ``max_sweeps`` caps the total
+    number of sweeps of a system: ``None`` = LAPACK's ``30 * max(10, nx)``, else 1 .. that number.
+
+    ``A [nb, nx, nx]``, ``B [nb, nx, nu]``, ``K [nb, nu, nx]`` (``nx <= 64``, ``nu <= 32``), float64 on the data's GPU; each may also
+    be its trailing block alone, shared by all problems - one nominal ``K [nu, nx]`` against per-environment ``A``, ``B`` is the
+    robustness sweep and costs no copy.  ``nb`` is taken and checked as in ``solve_dare``.  The leading axis may be strided (``A[:, 0]``
+    of ``linearize_rollout`` and ``sol.K`` are read in place); a trailing block that is not dense and row-major is copied once with
+    ``.contiguous()``; a negative stride is rejected.
+
+    **Order.**  ``wr, wi [nb, nx]`` by descending modulus, ties by descending ``wr``, then descending ``wi``; a complex pair comes as
+    exact conjugates (equal ``wr``, ``wi`` bitwise negated, the positive one first).  ``rho [nb]`` is the modulus of the first.
+
+    **Failures.**  ``status`` 1: an entry is not finite; 2: ``max_sweeps`` reached.  There ``wr``, ``wi`` are NaN and ``rho`` is
+    ``+inf``, so that ``rho < 1`` is false - deliberately not the zeros of ``solve_dare``, which would read as stable.  No other problem
+    is affected; a problem's results are bitwise the same at any position of any batch.  Enqueued on torch's current stream; nothing
+    waits for the GPU and nothing is copied to the host."""
+    import torch
+
+    fn = "closed_loop_poles"
+    sim = _sim(data)
+    dev = torch.device(f"cuda:{sim.device}")
+    if (B is None) != (K is None):
+        raise ConfigError(f"{fn}: B and K must be given together (both None: the poles of A)")
+    given = (("A", A),) if B is None else (("A", A), ("B", B), ("K", K))
+    for name, x in given:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != dev or x.ndim not in (2, 3):
+            raise ConfigError(f"{fn}: {name} must be a float64 torch tensor [nb, n, m] or [n, m] on {dev}")
+    nx = int(A.shape[-1])
+    nu = 0 if B is None else int(B.shape[-1])
+    if feedback_sign not in (-1, 1) or isinstance(feedback_sign, bool):
+        raise ConfigError(f"{fn}: feedback_sign must be -1 or +1")
+    if max_sweeps is not None and (isinstance(max_sweeps, bool) or int(max_sweeps) != max_sweeps or not 1 <= max_sweeps <= 30 * max(10, nx)):
+        raise ConfigError(f"{fn}: max_sweeps must be None or an integer in [1, {30 * max(10, nx)}]")
+    lead = {name: int(x.shape[0]) for name, x in given if x.ndim == 3}
+    if len(set(lead.values())) > 1:
+        raise ConfigError(f"{fn}: the leading sizes differ: {lead}")
+    nb = next(iter(lead.values())) if lead else 1
+    if nb < 1:
+        raise ConfigError(f"{fn}: at least one problem is required")
+    arrays, keep = {}, []
+    for (name, x), trail in zip(given, ((nx, nx), (nx, nu), (nu, nx))):
+        if tuple(x.shape[-2:]) != trail:
+            raise ConfigError(f"{fn}: {name} must have shape {[nb, *trail]} or {list(trail)}, got {list(x.shape)}")
+        if x.numel() and not (x[0] if x.ndim == 3 else x).is_contiguous():     # the trailing block must be dense, row-major
+            x = x.contiguous()
+        es = x.stride(0) if x.ndim == 3 else 0
+        if es < 0:
+            raise ConfigError(f"{fn}: {name} has a negative stride")
+        arrays[name] = (x.data_ptr(), 0, es); keep.append(x)
+    opt = dict(dtype=torch.float64, device=dev)
+    wr, wi, scale, rho = torch.empty((nb, nx), **opt), torch.empty((nb, nx), **opt), torch.empty((nb, nx), **opt), torch.empty((nb,), **opt)
+    sweeps, status = torch.empty((nb,), dtype=torch.int32, device=dev), torch.empty((nb,), dtype=torch.int32, device=dev)
+    sim.lqr_eig({"batch": nb, "nx": nx, "nu": nu, "feedback_sign": int(feedback_sign), "balance": int(bool(balance)),
+                 "max_sweeps": 0 if max_sweeps is None else int(max_sweeps)}, arrays,
+                {"wr": wr.data_ptr(), "wi": wi.data_ptr(), "rho": rho.data_ptr(), "scale": scale.data_ptr(), "sweeps": sweeps.data_ptr(),
+                 "status": status.data_ptr()}, keep=keep)
+    return PolesResult(wr, wi, rho, status, sweeps, scale)
+
+
 class TrajCostResult(NamedTuple):
     cost: object     # [B] float64; +inf where the sum is not finite
     cost_t: object   # [B, T + 1]
@@ -463,4 +552,4 @@ def select_candidates(data, cost, cand, *, mode: str = "argmin", temperature=Non
     return TrajSelectResult(u, best, best_cost, weights)
 
 
-__all__ = ["LqrBackwardResult", "LqrBoxResult", "lqr_backward", "lqr_candidates", "DareResult", "solve_dare","TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]
+__all__ = ["LqrBackwardResult", "LqrBoxResult", "lqr_backward", "lqr_candidates", "DareResult", "solve_dare", "PolesResult", "closed_loop_poles", "TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]
