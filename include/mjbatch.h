@@ -460,6 +460,49 @@ typedef struct mjbLqrEig {
 } mjbLqrEig;
 int mjb_lqr_eig(mjbData* d, const mjbLqrEig* p);
 
+/* ---- the infinite-horizon quadratic cost of running a gain on a batch of systems: the solution P of the discrete Lyapunov equation
+ *   P = M' P M + Q + K' R K,     M = A + feedback_sign * B K,     and     J = x0' P x0,
+ * the cost of u = u0 - K dx run for ever on (A, B).  For the optimal gain P is the X of mjb_lqr_dare - the P the reference's
+ * _solve_lqr_gains hands back beside K (examples/drone/controllers/lqr.py:350-360); for any other gain (a nominal one against every
+ * randomised (A_e, B_e), a hand-tuned one, the gain of a cheaper Q) it is scipy.linalg.solve_discrete_lyapunov, one system at a time on
+ * the host.  M is the closed loop whose spectral radius the reference checks (examples/drone/controllers/lqr.py:133-137, mjb_lqr_eig):
+ * that call answers "is it stable?", this one "what does it cost?".  With transpose != 0 the same iteration solves the Gramian form
+ * P = M P M' + S (S = B B' passed as Q: the controllability Gramian, the H2 norm).
+ * Squared Smith (doubling) iteration, per problem e in float64 (iterate k holds 2^k steps of the cost sum):
+ *   1. M = A + s B K, s = feedback_sign: -1 the convention of mjb_lqr_dare and mjb_set_feedback, +1 that of mjb_lqr_backward.  The sign
+ *      is applied to K exactly, so (+1, -K) is bitwise (-1, K).  B.ptr and K.ptr both NULL: M = A (nu is ignored); exactly one of them
+ *      NULL is an error.
+ *   2. S = sym(Q + K' (R K)).  R.ptr NULL, or no K: S = sym(Q); R without K is an error.  Q [nx, nx] and R [nu, nu] are taken as
+ *      symmetric and not checked: only their LOWER triangles are read.  An entry of M or S that is not finite ends with status 1.
+ *   3. P_0 = S, M_0 = M;  repeat k = 0, 1, ...:
+ *        T = M_k' (P_k M_k)                  (transpose != 0: T = M_k (P_k M_k'))
+ *        P_{k+1} = sym(P_k + T),  M_{k+1} = M_k M_k
+ *        change = max|P_{k+1} - P_k| / max|P_{k+1}|  (0 / 0 = 0);  iters += 1
+ *        an iterate that is not finite ends with status 2 (a closed loop with rho > 1 ends this way: M^(2^k) overflows);
+ *        the FIRST change <= tol ends with status 0;  iters == max_iter ends with status 3 (rho == 1 with a marginal mode S sees).
+ *      The stop is on change alone and at its first crossing, never on stagnation: with marginal modes that S does not see, change
+ *      collapses and then doubles with every further iteration.
+ *   4. P = P_k (bitwise symmetric);  with x0: J[e] = sum_i x0_i (P x0)_i, the row sums and the outer sum in index order.
+ * Inputs: A [nx, nx], B [nx, nu], K [nu, nx], Q [nx, nx], R [nu, nu], x0 [nx] per problem e at ptr + e * env_stride (step_stride
+ * ignored; env_stride 0 = shared by all problems: one K, Q, R against per-environment A, B is the robustness sweep, read without a
+ * copy).  nx <= 64, nu <= 32, 1 <= max_iter <= 64, tol >= 0: the kernel ends in bounded time on any input.
+ * Outputs, dense: P [batch, nx, nx]; J [batch], required exactly when x0.ptr is given; iters [batch] int32, status [batch] int32,
+ * change [batch] (NULL = not wanted).  For a non-zero status P[e] is NaN and J[e] is +inf, so that J < bound is false for a failed
+ * problem (the convention of mjb_lqr_eig, deliberately not the zeros of mjb_lqr_dare); iters[e] and change[e] hold what was reached
+ * (change = +inf when not finite); no other problem is affected.  A problem's results are bitwise the same at any position of any batch.
+ * Checks, launch and stream as mjb_lqr_dare / mjb_lqr_eig (MJB_ERR_ARG with a message before anything is launched, outputs
+ * untouched): sizes, feedback_sign, tol, max_iter, strides >= 0, required pointers, device memory of the data's device, the highest
+ * element inside its allocation; ONE kernel launch on the data's stream (one workgroup per problem, everything resident in LDS, the
+ * products on the f64 MFMA), no scratch memory, no host copy, no synchronisation. */
+typedef struct mjbLqrDlyap {
+  int batch, nx, nu, feedback_sign, transpose, max_iter;
+  double tol;
+  mjbStrided A, B, K, Q, R, x0;
+  double *P, *J, *change;
+  int *iters, *status;
+} mjbLqrDlyap;
+int mjb_lqr_dlyap(mjbData* d, const mjbLqrDlyap* p);
+
 /* ---- the quadratic trajectory cost, its first-order expansion and the choice among candidates: what an iLQR iteration or a sampling
  * planner needs between mjb_rollout_ctrl / mjb_transition_fd_points and mjb_lqr_backward / mjb_lqr_candidates, on the device.  The
  * reference's humanoid controller builds its Q in the 2nv tangent space (examples/humanoid/controllers/lqr.py:97-114) and takes the

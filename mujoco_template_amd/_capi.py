@@ -75,6 +75,13 @@ class LqrEigStruct(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("wr", "wi", "rho", "scale", "sweeps", "status")]
 
 
+class LqrDlyapStruct(ctypes.Structure):
+    """``mjbLqrDlyap`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("batch", "nx", "nu", "feedback_sign", "transpose", "max_iter")] + [("tol", ctypes.c_double)] + \
+               [(n, Strided) for n in ("A", "B", "K", "Q", "R", "x0")] + \
+               [(n, ctypes.c_void_p) for n in ("P", "J", "change", "iters", "status")]
+
+
 class StridedIn(ctypes.Structure):
     """``mjbStridedIn``: an ``mjbStrided`` array of float32 (dtype 0) or float64 (dtype 1) elements."""
     _fields_ = [("ptr", ctypes.c_void_p), ("step_stride", ctypes.c_long), ("env_stride", ctypes.c_long), ("dtype", ctypes.c_int)]
@@ -174,6 +181,8 @@ def load_library() -> ctypes.CDLL:
     L.mjb_lqr_dare.restype = ci
     L.mjb_lqr_eig.argtypes = [vp, ctypes.POINTER(LqrEigStruct)]
     L.mjb_lqr_eig.restype = ci
+    L.mjb_lqr_dlyap.argtypes = [vp, ctypes.POINTER(LqrDlyapStruct)]
+    L.mjb_lqr_dlyap.restype = ci
     L.mjb_lqr_gemm_tn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.mjb_lqr_gemm_tn.restype = ci
     L.mjb_traj_cost.argtypes = [vp, ctypes.POINTER(TrajCostStruct)]
@@ -1083,6 +1092,15 @@ class BatchSim:
         (0 = the default cap); ``arrays`` A and, together or not at all, B and K as (address, 0, env stride); ``pointers`` wr, wi, rho,
         scale, sweeps, status.  ``trajopt.closed_loop_poles`` is the checked tensor interface on top of it."""
         self._lqr_call(load_library().mjb_lqr_eig, LqrEigStruct(), sizes, arrays, pointers, keep)
+
+    def lqr_dlyap(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_lqr_dlyap`` on raw device addresses (see ``lqr_backward``): ``sizes`` batch, nx, nu, feedback_sign, transpose, max_iter,
+        tol; ``arrays`` A, Q and, where given, B, K, R, x0 as (address, 0, env stride) - an address of 0 is an absent array; ``pointers``
+        P, J (0 exactly when there is no x0), change (0 = not wanted), iters, status.  ``trajopt.closed_loop_cost`` is the checked tensor
+        interface on top of it."""
+        struct = LqrDlyapStruct()
+        struct.tol = float(sizes["tol"])
+        self._lqr_call(load_library().mjb_lqr_dlyap, struct, {k: v for k, v in sizes.items() if k != "tol"}, arrays, pointers, keep)
 
     def traj_cost(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
         """``mjb_traj_cost`` on raw device addresses (see ``lqr_backward``); the state and control entries of ``arrays`` carry a

@@ -21,6 +21,7 @@
 #include "mjb_lqr.hpp"
 #include "mjb_dare.hpp"
 #include "mjb_eig.hpp"
+#include "mjb_dlyap.hpp"
 #include "mjb_traj.hpp"
 
 using namespace mjb;
@@ -1778,6 +1779,45 @@ int mjb_lqr_eig(mjbData* d, const mjbLqrEig* p) {
   a.wr = p->wr; a.wi = p->wi; a.rho = p->rho; a.scale = p->scale; a.sweeps = p->sweeps; a.status = p->status;
   const hipError_t e = eig_launch(a, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_eig launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+// ---- mjb_lqr_dlyap: the checks (those of mjb_lqr_dare / mjb_lqr_eig); the kernels and their launch are in mjb_dlyap.hip ----
+int mjb_lqr_dlyap(mjbData* d, const mjbLqrDlyap* p) {
+  static const char* fn = "mjb_lqr_dlyap";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_lqr_dlyap: NULL argument");
+  static const char* const msg[8] = {"", ": batch must be >= 1", ": nx must lie in [1, 64] (the state the kernel keeps in LDS)", ": nu must lie in [1, 32]",
+                                     ": max_iter must lie in [1, 64]", ": tol must be >= 0", ": feedback_sign must be -1 or +1",
+                                     ": batch * nx * nx is too large"};
+  if ((p->B.ptr == nullptr) != (p->K.ptr == nullptr)) return fail(MJB_ERR_ARG, "mjb_lqr_dlyap: B and K must be given together (both NULL: M = A)");
+  const bool has_bk = p->B.ptr != nullptr;
+  if (p->R.ptr && !has_bk) return fail(MJB_ERR_ARG, "mjb_lqr_dlyap: R needs K (the cost term is K' R K)");
+  if ((p->x0.ptr == nullptr) != (p->J == nullptr)) return fail(MJB_ERR_ARG, "mjb_lqr_dlyap: x0 and J must be given together");
+  const int why = dlyap_size_error(p->batch, p->nx, p->nu, has_bk, p->max_iter, p->tol, p->feedback_sign);
+  if (why) return fail(MJB_ERR_ARG, std::string(fn) + msg[why]);
+  HIPCHK(hipSetDevice(d->device));
+  const long B = p->batch, nx = p->nx, nu = has_bk ? p->nu : 0;
+  int rc;
+  if ((rc = check_lqr_array(d, fn, "A", p->A.ptr, false, 1, B, nx * nx, 0, p->A.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "Q", p->Q.ptr, false, 1, B, nx * nx, 0, p->Q.env_stride)) != MJB_OK) return rc;
+  if (has_bk) {
+    if ((rc = check_lqr_array(d, fn, "B", p->B.ptr, false, 1, B, nx * nu, 0, p->B.env_stride)) != MJB_OK) return rc;
+    if ((rc = check_lqr_array(d, fn, "K", p->K.ptr, false, 1, B, nu * nx, 0, p->K.env_stride)) != MJB_OK) return rc;
+    if ((rc = check_lqr_array(d, fn, "R", p->R.ptr, true, 1, B, nu * nu, 0, p->R.env_stride)) != MJB_OK) return rc;
+  }
+  if ((rc = check_lqr_array(d, fn, "x0", p->x0.ptr, true, 1, B, nx, 0, p->x0.env_stride)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "P", p->P, false, 1, B, nx * nx, 0, nx * nx)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "J", p->J, true, 1, B, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "change", p->change, true, 1, B, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "iters", p->iters, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "status", p->status, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  DlyapArgs a;
+  a.B = p->batch; a.nx = p->nx; a.nu = (int)nu; a.transpose = p->transpose ? 1 : 0; a.max_iter = p->max_iter;
+  a.sign = (double)p->feedback_sign; a.tol = p->tol;
+  a.A = lqr_arr(p->A); a.Bm = lqr_arr(p->B); a.K = lqr_arr(p->K); a.Q = lqr_arr(p->Q); a.R = lqr_arr(p->R); a.x0 = lqr_arr(p->x0);
+  a.P = p->P; a.J = p->J; a.change = p->change; a.iters = p->iters; a.status = p->status;
+  const hipError_t e = dlyap_launch(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_dlyap launch: ") + hipGetErrorString(e));
   return MJB_OK;
 }
 

@@ -32,6 +32,16 @@ deflation tests), one wavefront per system - so the chain is ``... -> solve_dare
     stable = poles.rho < 1                                                       # False for a failed problem too: its rho is +inf
     # one nominal gain against every randomised model (K [nu, nx] is read once, no copy): closed_loop_poles(data, A[:, 0], B[:, 0], K_nominal)
 
+What a gain costs where it is stable is ``closed_loop_cost`` (``mjb_lqr_dlyap``): the solution ``P`` of the discrete Lyapunov equation
+``P = M' P M + Q + K' R K`` of the closed loop ``M = A - B K`` by the squared Smith (doubling) iteration, and ``J = x0' P x0``, one
+workgroup per system.  For the gain of ``solve_dare`` ``P`` is its ``X``; for the nominal gain on a randomised model it is what
+``scipy.linalg.solve_discrete_lyapunov`` gives on the host, so the chain goes on
+``... -> closed_loop_poles -> closed_loop_cost -> J_nominal / J_optimal per environment``::
+
+    nominal = closed_loop_cost(data, A[:, 0], B[:, 0], K_nominal, Q=Q, R=R, x0=dx0)        # P [B, nx, nx], J [B]; +inf where it failed
+    optimal = closed_loop_cost(data, A[:, 0], B[:, 0], sol.K, Q=Q, R=R, x0=dx0)            # P is sol.X to rounding
+    price = nominal.J / optimal.J                                                          # >= 1: what the nominal gain costs on model e
+
 Tensors are float64 on the data's GPU, addressed ``[B, T, ...]`` (``time_major=True``: ``[T, B, ...]``) through their own strides:
 the permuted views ``linearize_rollout`` returns, dense tensors of either order and ``expand``-ed ones are read in place.  A tensor of
 the trailing shape alone (``Q [nx, nx]``) is the same for every step and trajectory.  Only the two leading axes may be strided: the
@@ -393,6 +403,90 @@ def closed_loop_poles(data, A, B=None, K=None, *, feedback_sign: int = -1, balan
                 {"wr": wr.data_ptr(), "wi": wi.data_ptr(), "rho": rho.data_ptr(), "scale": scale.data_ptr(), "sweeps": sweeps.data_ptr(),
                  "status": status.data_ptr()}, keep=keep)
     return PolesResult(wr, wi, rho, status, sweeps, scale)
+
+
+class LyapResult(NamedTuple):
+    P: object        # [nb, nx, nx] the solution of P = M' P M + Q + K' R K, bitwise symmetric (NaN where status != 0)
+    J: object        # [nb] x0' P x0 (+inf where status != 0), or None without x0
+    status: object   # [nb] int32: 0 converged, 1 an entry of M or S is not finite, 2 an iterate not finite (rho > 1), 3 max_iter reached
+    iters: object    # [nb] int32 doubling iterations done
+    change: object   # [nb] max|P_{k+1} - P_k| / max|P_{k+1}| of the last iteration (+inf when not finite)
+
+
+def closed_loop_cost(data, A, B=None, K=None, *, Q, R=None, x0=None, feedback_sign: int = -1, transpose: bool = False,
+                     tol: float = 1e-12, max_iter: int = 64) -> LyapResult:
+    """The infinite-horizon quadratic cost of running the gain ``K`` on ``(A, B)`` for ``nb`` systems in one kernel launch
+    (``mjb_lqr_dlyap``): the solution ``P`` of the discrete Lyapunov equation
+
+        P = M' P M + Q + K' R K,        M = A + feedback_sign * B K
+
+    and, with ``x0``, ``J = x0' P x0`` - what ``scipy.linalg.solve_discrete_lyapunov`` gives for one system on the host.  For the
+    gain of ``solve_dare`` ``P`` is its ``X`` (the ``P`` the reference's ``_solve_lqr_gains`` returns beside ``K``); for any other gain
+    - a nominal one on a randomised model, a hand-tuned one - ``J / J_optimal`` says what that gain costs there.  The squared Smith
+    (doubling) iteration in float64 (include/mjbatch.h states it): ``P <- sym(P + M' P M)``, ``M <- M M``, so iterate ``k`` holds
+    ``2^k`` steps of the cost sum; it stops at the FIRST ``max|P_{k+1} - P_k| / max|P_{k+1}| <= tol`` or after ``max_iter`` (1..64).
+
+    **Sign.**  As in ``closed_loop_poles``: ``-1`` (the default) for the gains of ``solve_dare`` and ``set_feedback``, ``+1`` for
+    ``lqr_backward``'s; applied to ``K`` exactly.  With ``B`` and ``K`` both ``None``, ``M = A``; exactly one of them is a
+    ``ConfigError``, and so is ``R`` without ``K``.  ``R=None`` leaves the cost term ``K' R K`` out.
+
+    **Gramian form.**  ``transpose=True`` solves ``P = M P M' + S`` with the same ``S = sym(Q + K' R K)``: ``Q = B B'`` gives the
+    controllability Gramian of ``M``.
+
+    ``A [nb, nx, nx]``, ``B [nb, nx, nu]``, ``K [nb, nu, nx]``, ``Q [nb, nx, nx]``, ``R [nb, nu, nu]``, ``x0 [nb, nx]`` (``nx <= 64``,
+    ``nu <= 32``), float64 on the data's GPU; each may also be its trailing block alone, shared by all problems - one nominal ``K``,
+    ``Q``, ``R`` against per-environment ``A``, ``B`` is the robustness sweep and costs no copy.  ``nb`` is taken and checked as in
+    ``solve_dare``.  The leading axis may be strided (``A[:, 0]`` of ``linearize_rollout``, ``expand``-ed tensors and ``sol.K`` are read
+    in place); a trailing block that is not dense and row-major is copied once with ``.contiguous()``.  ``Q`` and ``R`` are taken as
+    symmetric and not checked: only their lower triangles are read.
+
+    **Failures.**  ``status`` 1: an entry of ``M`` or ``S`` is not finite; 2: an iterate is not finite (a closed loop with
+    ``rho > 1`` ends this way); 3: ``max_iter`` reached (``rho == 1`` with a marginal mode the cost sees).  There ``P`` is NaN and
+    ``J`` is ``+inf``, so that ``J < bound`` is false - the convention of ``closed_loop_poles``, not the zeros of ``solve_dare``;
+    ``iters`` and ``change`` hold what was reached.  No other problem is affected; a problem's results are bitwise the same at any
+    position of any batch.  Enqueued on torch's current stream; nothing waits for the GPU and nothing is copied to the host."""
+    import torch
+
+    fn = "closed_loop_cost"
+    sim = _sim(data)
+    dev = torch.device(f"cuda:{sim.device}")
+    if (B is None) != (K is None):
+        raise ConfigError(f"{fn}: B and K must be given together (both None: M = A)")
+    if R is not None and K is None:
+        raise ConfigError(f"{fn}: R needs K (the cost term is K' R K)")
+    for name, x in (("A", A), ("B", B), ("K", K), ("Q", Q), ("R", R)):
+        if x is not None and (not isinstance(x, torch.Tensor) or x.ndim not in (2, 3)):
+            raise ConfigError(f"{fn}: {name} must be a float64 torch tensor [nb, n, m] or [n, m] on {dev}")
+    if x0 is not None and (not isinstance(x0, torch.Tensor) or x0.ndim not in (1, 2)):
+        raise ConfigError(f"{fn}: x0 must be a float64 torch tensor [nb, nx] or [nx] on {dev}")
+    nx = int(A.shape[-1])
+    nu = 0 if B is None else int(B.shape[-1])
+    if feedback_sign not in (-1, 1) or isinstance(feedback_sign, bool):
+        raise ConfigError(f"{fn}: feedback_sign must be -1 or +1")
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= max_iter <= 64 or not (tol >= 0):
+        raise ConfigError(f"{fn}: max_iter must be an integer in [1, 64] and tol >= 0")
+    given = [("A", A, (nx, nx)), ("B", B, (nx, nu)), ("K", K, (nu, nx)), ("Q", Q, (nx, nx)), ("R", R, (nu, nu)), ("x0", x0, (nx,))]
+    lead = {name: int(x.shape[0]) for name, x, trail in given if x is not None and x.ndim == len(trail) + 1}
+    if len(set(lead.values())) > 1:
+        raise ConfigError(f"{fn}: the leading sizes differ: {lead}")
+    nb = next(iter(lead.values())) if lead else 1
+    if nb < 1:
+        raise ConfigError(f"{fn}: at least one problem is required")
+    arrays, keep = {}, []
+    for name, x, trail in given:                                   # one step per problem: [nb, 1, *trail] views through _strided
+        if x is not None and x.ndim == len(trail) + 1:
+            x = x.unsqueeze(1)
+        p, _, es, t = _strided(fn, name, x, trail, nb, 1, dev, False, optional=name in ("B", "K", "R", "x0"))
+        arrays[name] = (p, 0, es); keep.append(t)
+    opt = dict(dtype=torch.float64, device=dev)
+    P, change = torch.empty((nb, nx, nx), **opt), torch.empty((nb,), **opt)
+    J = None if x0 is None else torch.empty((nb,), **opt)
+    iters, status = torch.empty((nb,), dtype=torch.int32, device=dev), torch.empty((nb,), dtype=torch.int32, device=dev)
+    sim.lqr_dlyap({"batch": nb, "nx": nx, "nu": nu, "feedback_sign": int(feedback_sign), "transpose": int(bool(transpose)),
+                   "max_iter": int(max_iter), "tol": float(tol)}, arrays,
+                  {"P": P.data_ptr(), "J": 0 if J is None else J.data_ptr(), "change": change.data_ptr(), "iters": iters.data_ptr(),
+                   "status": status.data_ptr()}, keep=keep)
+    return LyapResult(P, J, status, iters, change)
 
 
 class TrajCostResult(NamedTuple):
