@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -390,38 +391,57 @@ struct EmitAlloc {
   // humanoid kernel (256 VGPRs) spills 61 VGPRs to scratch with the array form (spill stores around the ticket loop, ~7 KB per
   // environment and chunk switch: HBM write traffic 0.15 -> 1.2 GB per 1000-step launch) and far fewer with the struct form; it is
   // still 2 % faster with the arrays (4 % on the two-wave kernel).  The struct form is at commit a705124.
+  // Tables of records (stride S > 1, at least two records): the columns whose value is bitwise the same in every record become
+  // constants of the translation unit (mjb::UniformCols, mjb_types.hpp) - most solref / solimp / margin / range columns of a real
+  // model are defaults, and LLVM folds `tab[S * i + k]` only when the WHOLE table is one value.  Compared as emitted (after
+  // fill_dev_model's casts and clamps), bit for bit: +0.0 and -0.0 differ, a NaN column is never uniform.
+  struct Cols { int stride = 1; unsigned long long mask = 0; const char* ctype = ""; std::vector<std::string> val; };
   std::string text;
+  std::vector<Cols> cols;                                    // one per table, in emission order
   int n = 0;
   static constexpr unsigned long long TOKEN = 0x7E57AB1Eull << 32;
-  template <typename X, typename F> const X* emit(const std::vector<X>& v, const char* ctype, F fmt) {
+  template <typename X, typename F> const X* emit(const std::vector<X>& v, const char* ctype, int stride, F fmt) {
     std::string body;
     if (v.empty()) body = "0";
     for (size_t i = 0; i < v.size(); i++) { if (i) body += (i % 16 == 0 ? ",\n " : ","); body += fmt(v[i]); }
     text += std::string("static const __constant__ ") + ctype + " mjb_tab_" + std::to_string(n) + "[] = {" + body + "};\n";
+    Cols c;
+    c.ctype = ctype;
+    const size_t S = stride > 1 ? (size_t)stride : 1;
+    if (S > 1 && S <= 64 && v.size() % S == 0 && v.size() >= 2 * S) {
+      c.stride = (int)S;
+      c.val.assign(S, "0");
+      for (size_t k = 0; k < S; k++) {
+        bool same = v[k] == v[k];                            // false for a NaN
+        for (size_t r = 1; r * S < v.size() && same; r++) same = std::memcmp(&v[r * S + k], &v[k], sizeof(X)) == 0;
+        if (same) { c.mask |= 1ull << k; c.val[k] = fmt(v[k]); }
+      }
+    }
+    cols.push_back(c);
     return (const X*)(uintptr_t)(TOKEN + (unsigned long long)(n++) * 16ull + 16ull);
   }
-  const float* putf(const std::vector<float>& v) {
-    return emit(v, "float", [](float x) {
+  const float* putf(const std::vector<float>& v, int stride = 1) {
+    return emit(v, "float", stride, [](float x) {
       if (std::isnan(x)) return std::string("__builtin_nanf(\"\")");
       if (std::isinf(x)) return std::string(x > 0 ? "__builtin_inff()" : "-__builtin_inff()");
       char b[48]; std::snprintf(b, sizeof(b), "%af", (double)x); return std::string(b);             // hex float: exact
     });
   }
-  const double* putf(const std::vector<double>& v) {
-    return emit(v, "double", [](double x) {
+  const double* putf(const std::vector<double>& v, int stride = 1) {
+    return emit(v, "double", stride, [](double x) {
       if (std::isnan(x)) return std::string("__builtin_nan(\"\")");
       if (std::isinf(x)) return std::string(x > 0 ? "__builtin_inf()" : "-__builtin_inf()");
       char b[48]; std::snprintf(b, sizeof(b), "%a", x); return std::string(b);
     });
   }
-  const int* puti(const std::vector<int>& v) { return emit(v, "int", [](int x) { return std::to_string(x); }); }
-  const unsigned long long* putu(const std::vector<unsigned long long>& v) {
-    return emit(v, "unsigned long long", [](unsigned long long x) { char b[40]; std::snprintf(b, sizeof(b), "0x%llxull", x); return std::string(b); });
+  const int* puti(const std::vector<int>& v, int stride = 1) { return emit(v, "int", stride, [](int x) { return std::to_string(x); }); }
+  const unsigned long long* putu(const std::vector<unsigned long long>& v, int stride = 1) {
+    return emit(v, "unsigned long long", stride, [](unsigned long long x) { char b[40]; std::snprintf(b, sizeof(b), "0x%llxull", x); return std::string(b); });
   }
 };
 
 template <typename T>
-std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max) {
+std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max, int prm_mask) {
   static_assert(sizeof(DevModel<T>) % 8 == 0, "DevModel<T> is written out in 8-byte words");
   const char* tname = sizeof(T) == 4 ? "float" : "double";
   EmitAlloc ea;
@@ -460,6 +480,39 @@ std::string baked_model_source(const HostModel& h, int ncon_max, int nefc_max) {
   }
   std::string s = "#include \"mjb_types.hpp\"\n// the model as constant data of this translation unit (tables, then the DevModel image)\n";
   s += ea.text + decl + init;
+  {
+    // the uniform columns of the record tables the kernels read through MJB_REC (mjb_device.hpp), keyed by the pointer word of the
+    // table in DevModel, so that MJB_REC finds them from the member it reads.  This list names those tables: a table that is not in
+    // it gets no constants and is read as before (a missing entry costs a fold, never a wrong value).  A field that is batched per
+    // environment in this kernel (prm_mask) is read from the environment's rows: no constants for its table, for the tables derived
+    // from it, or for the record column that holds a copy of it.
+    struct Named { size_t off; const char* name; int prm; unsigned long long drop; };
+#define NM(f, prm, drop) {offsetof(DevModel<T>, f), #f, prm, drop}
+    const Named named[] = {
+        NM(body_pos, -1, 0), NM(body_quat, -1, 0), NM(body_ipos, -1, 0), NM(body_iquat, -1, 0), NM(geom_size, -1, 0), NM(actuator_trnid, -1, 0),
+        NM(actuator_gear, PRM_ACT_GEAR, ~0ull), NM(actuator_gainprm, PRM_ACT_GAINPRM, ~0ull), NM(actuator_biasprm, PRM_ACT_BIASPRM, ~0ull),
+        NM(actuator_ctrlrange, -1, 0), NM(actuator_forcerange, -1, 0), NM(pair_friction, PRM_GEOM_FRICTION, ~0ull),
+        NM(pair_kb, -1, 0), NM(lim_f, -1, 0), NM(jnt_rec, -1, 0), NM(jnt_irec, -1, 0), NM(dof_irec, -1, 0),
+        NM(dof_frec, PRM_DOF_DAMPING, 1ull), NM(body_irec, -1, 0), NM(pair_body, -1, 0), NM(lim_i, -1, 0)};
+#undef NM
+    for (size_t i = 0; i < nw; i++) {
+      if ((wv[i] >> 32) != (EmitAlloc::TOKEN >> 32)) continue;
+      const EmitAlloc::Cols& c = ea.cols[(size_t)((wv[i] - EmitAlloc::TOKEN) / 16 - 1)];
+      const Named* nm = nullptr;
+      for (const Named& x : named) if (x.off == 8 * i) nm = &x;
+      if (!nm) continue;
+      unsigned long long mask = c.mask;
+      if (nm->prm >= 0 && ((prm_mask >> nm->prm) & 1)) mask &= ~nm->drop;
+      if (!mask) continue;
+      char hex[24];
+      std::snprintf(hex, sizeof(hex), "0x%llxull", mask);
+      s += std::string("// uniform columns of ") + nm->name + " (stride " + std::to_string(c.stride) + ")\ntemplate <> struct mjb::UniformCols<" + std::to_string(i) +
+           "> { static constexpr unsigned long long mask = " + hex + ";";
+      s += std::string(" static constexpr ") + c.ctype + " val[" + std::to_string(c.stride) + "] = {";
+      for (int k = 0; k < c.stride; k++) s += (k ? ", " : "") + ((mask >> k) & 1 ? c.val[(size_t)k] : std::string("0"));
+      s += "}; };\n";
+    }
+  }
   s += std::string("static_assert(sizeof(MjbBakedModel) == sizeof(mjb::DevModel<") + tname + ">), \"baked model image\");\n";
   s += std::string("#define MJB_SPEC_BAKED (*(const mjb::DevModel<") + tname + "> MJB_CONST*)&mjb_baked_model)\n";
   return s;
@@ -509,7 +562,7 @@ std::string spec_source(const HostModel& h_model, const Config& c, int dtype, in
     }
     if (le2) s += "#define MJB_SPEC_SOLIMP_POWER_1_OR_2 1\n";       // (model fields are read-only after compilation: only the solver options change at run time)
   }
-  s += kind != MJB_KERNEL_FD ? baked_model_source<float>(h, ncon_max, nefc_max) : baked_model_source<double>(h, ncon_max, nefc_max);
+  s += kind != MJB_KERNEL_FD ? baked_model_source<float>(h, ncon_max, nefc_max, prm_mask) : baked_model_source<double>(h, ncon_max, nefc_max, prm_mask);
   s += "#include \"mjb_kernels.hpp\"\n";
   if (prm_mask) s += "extern \"C\" __constant__ int mjb_spec_params = " + std::to_string(prm_mask) + ";   // checked by mjb_kernel_load\n";
   return s;

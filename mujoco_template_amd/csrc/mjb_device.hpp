@@ -17,6 +17,7 @@
 // kernel logic without a GPU; the product library never contains that build.
 #pragma once
 #include "mjb_types.hpp"
+#include <cstddef>
 
 #ifdef MJB_HOST_EMU
 #include <cmath>
@@ -564,6 +565,52 @@ MJB_DEV void tile_factor(MRef m, const T* M, T* W, T* dinv, T* col, const T* J, 
 #define MJB_MODEL_OF(p) (*(p))
 #endif
 #define MJB_OPT(c, f) ((*(c).mp).f)
+// MJB_REC(m, f, S, i, k): column k of record i of the record table m.f (S values per record) - the ONE accessor of record reads
+// whose column is a compile-time constant (after unrolling).  In a translation unit with a baked model a column that holds the
+// same bits in every record is a constant of the unit (UniformCols, mjb_types.hpp) and the read returns it: the VALUE is
+// substituted, the expression around it stays as written, so the compiler drops only what IEEE arithmetic lets it drop and the
+// results are those of the table read.  Generic kernels, the host emulation and a model that was not baked: the table read itself.
+#if defined(MJB_SPEC_BAKED) && !defined(MJB_HOST_EMU)
+template <typename TP> struct RecElem;
+template <typename E> struct RecElem<const E MJB_CONST*> { typedef E type; };
+template <int W, int S, typename TP> MJB_DEV typename RecElem<TP>::type rec_get(TP tab, int i, int k) {
+  if constexpr (UniformCols<W>::mask != 0) {
+    if ((UniformCols<W>::mask >> k) & 1) return UniformCols<W>::val[k];
+  }
+  return tab[S * i + k];
+}
+// (the word of m.f in the DevModel type of m itself: no reliance on what the template parameter at the use is called)
+template <typename M> struct RecModel;
+template <typename E> struct RecModel<const DevModel<E> MJB_CONST&> { typedef DevModel<E> type; };
+#define MJB_REC_W(m, f) ((int)(offsetof(typename mjb::RecModel<decltype(m)>::type, f) / 8))
+#define MJB_REC(m, f, S, i, k) (mjb::rec_get<MJB_REC_W(m, f), (S)>((m).f, (i), (k)))
+// MJB_REC_PIN(m, f, k, v): v was read from column k of SOME record of m.f on another control path (a value merged from several
+// branches, of which the compiler no longer knows that it is the column's constant): the constant again where the column is uniform,
+// else v.  MJB_REC_PIN2: v came from column k1 of m.f1 or from column k2 of m.f2 - the constant where both columns are uniform and
+// hold the same bits.  Used where one instance of code serves the records of two tables (make_constraint).
+MJB_DEV bool rec_same_bits(float a, float b) { return __builtin_bit_cast(unsigned, a) == __builtin_bit_cast(unsigned, b); }
+MJB_DEV bool rec_same_bits(double a, double b) { return __builtin_bit_cast(unsigned long long, a) == __builtin_bit_cast(unsigned long long, b); }
+MJB_DEV bool rec_same_bits(int a, int b) { return a == b; }
+template <int W, typename E> MJB_DEV E rec_pin(E v, int k) {
+  if constexpr (UniformCols<W>::mask != 0) {
+    if ((UniformCols<W>::mask >> k) & 1) return UniformCols<W>::val[k];
+  }
+  return v;
+}
+template <int W1, int W2, typename E> MJB_DEV E rec_pin2(E v, int k1, int k2) {
+  if constexpr (UniformCols<W1>::mask != 0 && UniformCols<W2>::mask != 0) {
+    if (((UniformCols<W1>::mask >> k1) & 1) && ((UniformCols<W2>::mask >> k2) & 1) && rec_same_bits(UniformCols<W1>::val[k1], UniformCols<W2>::val[k2]))
+      return UniformCols<W1>::val[k1];
+  }
+  return v;
+}
+#define MJB_REC_PIN(m, f, k, v) (mjb::rec_pin<MJB_REC_W(m, f)>((v), (k)))
+#define MJB_REC_PIN2(m, f1, k1, f2, k2, v) (mjb::rec_pin2<MJB_REC_W(m, f1), MJB_REC_W(m, f2)>((v), (k1), (k2)))
+#else
+#define MJB_REC(m, f, S, i, k) ((m).f[(S) * (i) + (k)])
+#define MJB_REC_PIN(m, f, k, v) (v)
+#define MJB_REC_PIN2(m, f1, k1, f2, k2, v) (v)
+#endif
 #ifdef MJB_HOST_EMU
 #define MJB_ENV(c) ModelRef<T> m = *(c).mp; LayRef L = *(c).lp
 #else
@@ -643,6 +690,15 @@ MJB_DEV T prm_get(const Ctx<T>& c, TP tab, int n, int i, int ti) {
   }
   return tab[ti];
 }
+// the same two reads where the model's value is column k of record i of a record table (MJB_PRM_REC / MJB_PRM_GET_REC): an unbatched
+// field of a specialised kernel reads through MJB_REC (a uniform column folds), everything else is prm_row / prm_get as above
+#if defined(MJB_SPEC_BAKED) && !defined(MJB_HOST_EMU)
+#define MJB_PRM_REC(K, c, m, f, S, n, i, k) (MJB_PRM_ON(mjb::prm_src<K>()) ? mjb::prm_row<K>(c, (m).f, n)[(S) * (i) + (k)] : MJB_REC(m, f, S, i, k))
+#define MJB_PRM_GET_REC(K, c, m, f, S, n, i, k) (MJB_PRM_ON(mjb::prm_src<K>()) ? mjb::prm_get<K>(c, (m).f, n, i, (S) * (i) + (k)) : MJB_REC(m, f, S, i, k))
+#else
+#define MJB_PRM_REC(K, c, m, f, S, n, i, k) (mjb::prm_row<K>(c, (m).f, n)[(S) * (i) + (k)])
+#define MJB_PRM_GET_REC(K, c, m, f, S, n, i, k) (mjb::prm_get<K>(c, (m).f, n, i, (S) * (i) + (k)))
+#endif
 // has_damping of this data: the model's, or per-environment damping (then the implicit-damping path runs for every environment)
 template <typename T> MJB_DEV bool has_damping(const Ctx<T>& c, int model_has_damping) {
   if constexpr (MJB_PRM_ON(PRM_DOF_DAMPING)) {
@@ -1275,10 +1331,10 @@ template <typename T, int G> MJB_DEV void kinematics(Ctx<T>& c) {
   }
   // (1) local poses; xpos/xquat/xanchor/xaxis temporarily hold parent-frame values
   for (int b = 1 + lane; b < m.nbody; b += G) {
-    const int jadr = m.body_irec[4 * b], jnum = m.body_irec[4 * b + 1], jt0 = m.body_irec[4 * b + 2];
+    const int jadr = MJB_REC(m, body_irec, 4, b, 0), jnum = MJB_REC(m, body_irec, 4, b, 1), jt0 = MJB_REC(m, body_irec, 4, b, 2);
     T pos[3], quat[4], R[9];
     if (jnum == 1 && jt0 == JNT_FREE) {
-      int qa = m.jnt_irec[6 * jadr + 1];
+      int qa = MJB_REC(m, jnt_irec, 6, jadr, 1);
       quat[0] = qpos[qa + 3]; quat[1] = qpos[qa + 4]; quat[2] = qpos[qa + 5]; quat[3] = qpos[qa + 6];
       quat_normalize(quat);
       qpos[qa + 3] = quat[0]; qpos[qa + 4] = quat[1]; qpos[qa + 5] = quat[2]; qpos[qa + 6] = quat[3];
@@ -1287,15 +1343,15 @@ template <typename T, int G> MJB_DEV void kinematics(Ctx<T>& c) {
       xaxis[3 * jadr] = 0; xaxis[3 * jadr + 1] = 0; xaxis[3 * jadr + 2] = 1;
     } else {
 #pragma unroll
-      for (int k = 0; k < 3; k++) pos[k] = m.body_pos[3 * b + k];
+      for (int k = 0; k < 3; k++) pos[k] = MJB_REC(m, body_pos, 3, b, k);
 #pragma unroll
-      for (int k = 0; k < 4; k++) quat[k] = m.body_quat[4 * b + k];
+      for (int k = 0; k < 4; k++) quat[k] = MJB_REC(m, body_quat, 4, b, k);
       quat2mat(R, quat);                                       // R follows quat through the joints: formed once per change, not twice
       for (int j = jadr; j < jadr + jnum; j++) {
-        T jp[3] = {m.jnt_rec[8 * j], m.jnt_rec[8 * j + 1], m.jnt_rec[8 * j + 2]};
-        T ja[3] = {m.jnt_rec[8 * j + 3], m.jnt_rec[8 * j + 4], m.jnt_rec[8 * j + 5]};
-        const int jtype = m.jnt_irec[6 * j], qa = m.jnt_irec[6 * j + 1];
-        T val = qpos[qa] - m.jnt_rec[8 * j + 6];
+        T jp[3] = {MJB_REC(m, jnt_rec, 8, j, 0), MJB_REC(m, jnt_rec, 8, j, 1), MJB_REC(m, jnt_rec, 8, j, 2)};
+        T ja[3] = {MJB_REC(m, jnt_rec, 8, j, 3), MJB_REC(m, jnt_rec, 8, j, 4), MJB_REC(m, jnt_rec, 8, j, 5)};
+        const int jtype = MJB_REC(m, jnt_irec, 6, j, 0), qa = MJB_REC(m, jnt_irec, 6, j, 1);
+        T val = qpos[qa] - MJB_REC(m, jnt_rec, 8, j, 6);
         T anchor[3], axis[3];
         mulmatvec3(anchor, R, jp);
         anchor[0] += pos[0]; anchor[1] += pos[1]; anchor[2] += pos[2];
@@ -1396,8 +1452,8 @@ template <typename T, int G> MJB_DEV void kinematics(Ctx<T>& c) {
 #pragma unroll
     for (int k = 0; k < 4; k++) quat[k] = xquat[4 * b + k];
     quat2mat(R, quat);
-    T ip[3] = {m.body_ipos[3 * b], m.body_ipos[3 * b + 1], m.body_ipos[3 * b + 2]};
-    T iq[4] = {m.body_iquat[4 * b], m.body_iquat[4 * b + 1], m.body_iquat[4 * b + 2], m.body_iquat[4 * b + 3]};
+    T ip[3] = {MJB_REC(m, body_ipos, 3, b, 0), MJB_REC(m, body_ipos, 3, b, 1), MJB_REC(m, body_ipos, 3, b, 2)};
+    T iq[4] = {MJB_REC(m, body_iquat, 4, b, 0), MJB_REC(m, body_iquat, 4, b, 1), MJB_REC(m, body_iquat, 4, b, 2), MJB_REC(m, body_iquat, 4, b, 3)};
     mulmatvec3(t, R, ip);
     quat_mul(q2, quat, iq);
     quat2mat(R2, q2);
@@ -1407,8 +1463,8 @@ template <typename T, int G> MJB_DEV void kinematics(Ctx<T>& c) {
     for (int k = 0; k < 9; k++) { xmat[9 * b + k] = R[k]; ximat[9 * b + k] = R2[k]; }
   }
   for (int j = lane; j < m.njnt; j += G) {
-    if (m.jnt_irec[6 * j] == JNT_FREE) continue;                // already world values (the parent is the world body)
-    int p = m.jnt_irec[6 * j + 4];
+    if (MJB_REC(m, jnt_irec, 6, j, 0) == JNT_FREE) continue;                // already world values (the parent is the world body)
+    int p = MJB_REC(m, jnt_irec, 6, j, 4);
     T pq[4], R[9], a[3], ax[3], la[3] = {xanchor[3 * j], xanchor[3 * j + 1], xanchor[3 * j + 2]}, lx[3] = {xaxis[3 * j], xaxis[3 * j + 1], xaxis[3 * j + 2]};
 #pragma unroll
     for (int k = 0; k < 4; k++) pq[k] = xquat[4 * p + k];
@@ -1485,7 +1541,7 @@ template <typename T, int G> MJB_DEV void com_pos(Ctx<T>& c) {
   }
   T *cdof = w + L.cdof, *xanchor = w + L.xanchor, *xaxis = w + L.xaxis;
   for (int j = lane; j < m.njnt; j += G) {
-    int b = m.jnt_irec[6 * j + 3], da = m.jnt_irec[6 * j + 2], r = m.jnt_irec[6 * j + 5], jt = m.jnt_irec[6 * j];
+    int b = MJB_REC(m, jnt_irec, 6, j, 3), da = MJB_REC(m, jnt_irec, 6, j, 2), r = MJB_REC(m, jnt_irec, 6, j, 5), jt = MJB_REC(m, jnt_irec, 6, j, 0);
     T off[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) off[k] = sc[3 * r + k] - xanchor[3 * j + k];
@@ -1622,8 +1678,8 @@ template <typename T, int G> MJB_DEV void collide_pass(Ctx<T>& c, int p, bool va
       int g1 = m.pair_geom1[p], g2 = m.pair_geom2[p], t1 = m.geom_type[g1], t2 = m.geom_type[g2];
       T margin = m.pair_margin[p];
       T p1[3] = {gx[3 * g1], gx[3 * g1 + 1], gx[3 * g1 + 2]}, p2[3] = {gx[3 * g2], gx[3 * g2 + 1], gx[3 * g2 + 2]};
-      T s1[3] = {m.geom_size[3 * g1], m.geom_size[3 * g1 + 1], m.geom_size[3 * g1 + 2]};
-      T s2[3] = {m.geom_size[3 * g2], m.geom_size[3 * g2 + 1], m.geom_size[3 * g2 + 2]};
+      T s1[3] = {MJB_REC(m, geom_size, 3, g1, 0), MJB_REC(m, geom_size, 3, g1, 1), MJB_REC(m, geom_size, 3, g1, 2)};
+      T s2[3] = {MJB_REC(m, geom_size, 3, g2, 0), MJB_REC(m, geom_size, 3, g2, 1), MJB_REC(m, geom_size, 3, g2, 2)};
       T z1[3] = {gm[9 * g1 + 2], gm[9 * g1 + 5], gm[9 * g1 + 8]}, z2[3] = {gm[9 * g2 + 2], gm[9 * g2 + 5], gm[9 * g2 + 8]};
       if (t1 == G_PLANE) {
         if (t2 == G_SPHERE) n = nc_plane_sphere(p1, z1, p2, s2[0], margin, rc[0]);
@@ -1742,7 +1798,7 @@ template <typename T, int G> MJB_DEV void collide_pass(Ctx<T>& c, int p, bool va
           o[0] = r.dist; o[1] = r.pos[0]; o[2] = r.pos[1]; o[3] = r.pos[2];
 #pragma unroll
           for (int a = 0; a < 6; a++) o[4 + a] = f[a];
-          o[10] = prm_row<PRM_PAIR_FRICTION>(c, m.pair_friction, 5 * m.npair)[5 * p];
+          o[10] = MJB_PRM_REC(PRM_PAIR_FRICTION, c, m, pair_friction, 5, 5 * m.npair, p, 0);
           con_pair[slot] = p;
         }
       }
@@ -1882,10 +1938,10 @@ template <typename T, int G> MJB_DEV void make_constraint(Ctx<T>& c) {
     T dist = 0, dist2 = 0, margin = 0, mu = 0;
     bool both = false;
     if (isl) {
-      if (m.lim_i[2 * k]) {                                     // one record per limit object: no index hops
-        const T value = isj ? qpos[m.lim_i[2 * k + 1]] : tl[m.lim_i[2 * k + 1]];
-        margin = m.lim_f[12 * k + 2];
-        const T d0 = value - m.lim_f[12 * k], d1 = m.lim_f[12 * k + 1] - value;
+      if (MJB_REC(m, lim_i, 2, k, 0)) {                                     // one record per limit object: no index hops
+        const T value = isj ? qpos[MJB_REC(m, lim_i, 2, k, 1)] : tl[MJB_REC(m, lim_i, 2, k, 1)];
+        margin = MJB_REC(m, lim_f, 12, k, 2);
+        const T d0 = value - MJB_REC(m, lim_f, 12, k, 0), d1 = MJB_REC(m, lim_f, 12, k, 1) - value;
         const bool a0 = d0 < margin, a1 = d1 < margin;
         cnt = (int)a0 + (int)a1;
         both = a0 && a1;                                        // only where the range is narrower than twice the margin
@@ -1894,7 +1950,7 @@ template <typename T, int G> MJB_DEV void make_constraint(Ctx<T>& c) {
     } else if (k < nitem) {
       p = con_pair[ci] & 0xffff;
       dist = con[ci * CON_STRIDE]; mu = con[ci * CON_STRIDE + 10];
-      margin = m.pair_kb[PAIR_KB_STRIDE * p];
+      margin = MJB_REC(m, pair_kb, PAIR_KB_STRIDE, p, 0);
       if (dist < margin) cnt = m.pair_condim[p] == 1 ? 1 : 4;
     }
     int total, off = gscan_small<G>(cnt, lane, total);
@@ -1911,24 +1967,26 @@ template <typename T, int G> MJB_DEV void make_constraint(Ctx<T>& c) {
         type = (isj ? EFC_LIMIT_JOINT : EFC_LIMIT_TENDON) | (((isj ? k : k - m.njnt) * 2 + sd) << 9);
       }
       if (emit || both) {
-        diag = m.lim_f[12 * k + 3]; K = m.lim_f[12 * k + 4]; B = m.lim_f[12 * k + 5];
+        diag = MJB_REC(m, lim_f, 12, k, 3); K = MJB_REC(m, lim_f, 12, k, 4); B = MJB_REC(m, lim_f, 12, k, 5);
 #pragma unroll
-        for (int q = 0; q < 5; q++) si[q] = m.lim_f[12 * k + 6 + q];
+        for (int q = 0; q < 5; q++) si[q] = MJB_REC(m, lim_f, 12, k, 6 + q);
       }
     } else if (k < nitem) {
       emit = cnt > 0 && row + cnt <= cap;
       con_pair[ci] = p | ((emit ? row + 1 : 0) << 16);          // bits 16..: first constraint row + 1 (0 = none)
       if (emit) {
-        const T tran = m.pair_kb[PAIR_KB_STRIDE * p + 1];
-        K = m.pair_kb[PAIR_KB_STRIDE * p + 2]; B = m.pair_kb[PAIR_KB_STRIDE * p + 3];
+        const T tran = MJB_REC(m, pair_kb, PAIR_KB_STRIDE, p, 1);
+        K = MJB_REC(m, pair_kb, PAIR_KB_STRIDE, p, 2); B = MJB_REC(m, pair_kb, PAIR_KB_STRIDE, p, 3);
 #pragma unroll
-        for (int q = 0; q < 5; q++) si[q] = m.pair_kb[PAIR_KB_STRIDE * p + 4 + q];
+        for (int q = 0; q < 5; q++) si[q] = MJB_REC(m, pair_kb, PAIR_KB_STRIDE, p, 4 + q);
         if (cnt == 1) diag = tran; else diag = tran + mu * mu * tran;
         type = (cnt == 1 ? EFC_CONTACT_FRICTIONLESS : EFC_CONTACT_PYRAMIDAL) | (ci << 9);
       }
     }
     if (emit) {
       T imp, R;
+#pragma unroll
+      for (int q = 0; q < 5; q++) si[q] = MJB_REC_PIN2(m, lim_f, 6 + q, pair_kb, 4 + q, si[q]);   // one instance of the impedance code for both record kinds
       row_imp_R(dist, margin, si, diag, imp, R);
       int nr = 1;
       if (!isl && cnt == 4) {
@@ -1949,6 +2007,8 @@ template <typename T, int G> MJB_DEV void make_constraint(Ctx<T>& c) {
     if (base < nobj && gany<G>(both)) {                         // the upper side of a limit object with both sides active: a second trip
       if (both && row + 1 < cap) {
         T imp, R;
+#pragma unroll
+        for (int q = 0; q < 5; q++) si[q] = MJB_REC_PIN(m, lim_f, 6 + q, si[q]);
         row_imp_R(dist2, margin, si, diag, imp, R);
         etype[row + 1] = type + (1 << 9);
         epos[row + 1] = dist2; emargin[row + 1] = margin; eD[row + 1] = 1 / R; eK[row + 1] = K; eB[row + 1] = B; eI[row + 1] = imp;
@@ -1993,7 +2053,7 @@ template <typename T, int G> MJB_DEV void make_constraint(Ctx<T>& c) {
       int row = (con_pair[ci] >> 16) - 1;
       if (row < 0) continue;
       int p = con_pair[ci] & 0xffff;
-      int b1 = m.pair_body[2 * p], b2 = m.pair_body[2 * p + 1];
+      int b1 = MJB_REC(m, pair_body, 2, p, 0), b2 = MJB_REC(m, pair_body, 2, p, 1);
       const T* cc = con + ci * CON_STRIDE;
       // column of body 2 minus column of body 1: a dof that moves both (the same column twice) or neither gives exactly +0, a dof
       // that moves one of them gives that body's column, as +col - 0 or 0 - col
@@ -2061,7 +2121,7 @@ template <typename T, int G> MJB_DEV void vel_bias_passive(Ctx<T>& c) {
   gsync<G>();
   tree_forward_sum<T, G, 6>(c, cvel);
   for (int j = lane; j < nv; j += G) {
-    const int p = m.dof_irec[6 * j + 1], first = m.dof_irec[6 * j + 2], gs = m.dof_irec[6 * j + 3];   // one record: no index hops
+    const int p = MJB_REC(m, dof_irec, 6, j, 1), first = MJB_REC(m, dof_irec, 6, j, 2), gs = MJB_REC(m, dof_irec, 6, j, 3);   // one record: no index hops
     T tmp[6] = {0, 0, 0, 0, 0, 0};
     if (gs >= 0) {                                              // gs < 0: translational dof of a free joint, cdof_dot = 0
       // gs: the three rotations of a free joint share the velocity after its translations; every other dof starts at itself
@@ -2158,13 +2218,13 @@ template <typename T, int G> MJB_DEV void vel_bias_passive(Ctx<T>& c) {
   }
   T *qb = w + L.qfrc_bias, *qp = w + L.qfrc_passive;
   for (int i = lane; i < nv; i += G) {
-    const int b = m.dof_irec[6 * i], qa = m.dof_irec[6 * i + 4];
+    const int b = MJB_REC(m, dof_irec, 6, i, 0), qa = MJB_REC(m, dof_irec, 6, i, 4);
     T v = 0;
 #pragma unroll
     for (int k = 0; k < 6; k++) v += cdof[6 * i + k] * cfrc[6 * b + k];
     qb[i] = v;
-    T pf = -prm_get<PRM_DOF_DAMPING>(c, m.dof_frec, nv, i, 4 * i) * qvel[i];          // damping: the dof record holds the model's
-    if (qa >= 0) pf -= m.dof_frec[4 * i + 1] * (qpos[qa] - m.dof_frec[4 * i + 2]);      // hinge / slide spring
+    T pf = -MJB_PRM_GET_REC(PRM_DOF_DAMPING, c, m, dof_frec, 4, nv, i, 0) * qvel[i];          // damping: the dof record holds the model's
+    if (qa >= 0) pf -= MJB_REC(m, dof_frec, 4, i, 1) * (qpos[qa] - MJB_REC(m, dof_frec, 4, i, 2));      // hinge / slide spring
     if (m.has_fluid) {
       T* xipos = w + L.xipos;
       for (int bb = 1; bb < m.nbody; bb++) {
@@ -2191,20 +2251,20 @@ template <typename T, int G> MJB_DEV void actuation_forces(Ctx<T>& c) {
     T force = 0;
     if (!(grp >= 0 && grp < 31 && ((MJB_OPT(c, disableactuator) >> grp) & 1))) {
       T u = ctrl[a];
-      if (m.actuator_ctrllimited[a]) u = t_min(t_max(u, m.actuator_ctrlrange[2 * a]), m.actuator_ctrlrange[2 * a + 1]);
-      force = prm_row<PRM_ACT_GAINPRM>(c, m.actuator_gainprm, 3 * m.nu)[3 * a] * u;
+      if (m.actuator_ctrllimited[a]) u = t_min(t_max(u, MJB_REC(m, actuator_ctrlrange, 2, a, 0)), MJB_REC(m, actuator_ctrlrange, 2, a, 1));
+      force = MJB_PRM_REC(PRM_ACT_GAINPRM, c, m, actuator_gainprm, 3, 3 * m.nu, a, 0) * u;
       if (m.actuator_biastype[a] == 1) {
         T len = 0, vel = 0;
         if (m.actuator_trntype[a] == TRN_JOINT) {
-          int j = m.actuator_trnid[2 * a];
-          const T MJB_CONST* gear = prm_row<PRM_ACT_GEAR>(c, m.actuator_gear, 6 * m.nu);
-          len = gear[6 * a] * qpos[m.jnt_qposadr[j]];
-          vel = gear[6 * a] * qvel[m.jnt_dofadr[j]];
+          int j = MJB_REC(m, actuator_trnid, 2, a, 0);
+          const T gear0 = MJB_PRM_REC(PRM_ACT_GEAR, c, m, actuator_gear, 6, 6 * m.nu, a, 0);
+          len = gear0 * qpos[m.jnt_qposadr[j]];
+          vel = gear0 * qvel[m.jnt_dofadr[j]];
         }
-        const T MJB_CONST* bias = prm_row<PRM_ACT_BIASPRM>(c, m.actuator_biasprm, 3 * m.nu);
-        force += bias[3 * a] + bias[3 * a + 1] * len + bias[3 * a + 2] * vel;
+        force += MJB_PRM_REC(PRM_ACT_BIASPRM, c, m, actuator_biasprm, 3, 3 * m.nu, a, 0) + MJB_PRM_REC(PRM_ACT_BIASPRM, c, m, actuator_biasprm, 3, 3 * m.nu, a, 1) * len +
+                 MJB_PRM_REC(PRM_ACT_BIASPRM, c, m, actuator_biasprm, 3, 3 * m.nu, a, 2) * vel;
       }
-      if (m.actuator_forcelimited[a]) force = t_min(t_max(force, m.actuator_forcerange[2 * a]), m.actuator_forcerange[2 * a + 1]);
+      if (m.actuator_forcelimited[a]) force = t_min(t_max(force, MJB_REC(m, actuator_forcerange, 2, a, 0)), MJB_REC(m, actuator_forcerange, 2, a, 1));
     }
     af[a] = force;
   }
@@ -2213,14 +2273,13 @@ template <typename T, int G> MJB_DEV void actuation_forces(Ctx<T>& c) {
   T *sx = w + L.site_xpos, *sm = w + L.site_xmat;
   for (int i = lane; i < nv; i += G) {
     T s = 0;
-    const T MJB_CONST* gear = prm_row<PRM_ACT_GEAR>(c, m.actuator_gear, 6 * m.nu);
-    for (int k = m.dofact_adr[i]; k < m.dofact_adr[i + 1]; k++) { int a = m.dofact_act[k]; s += gear[6 * a] * af[a]; }
+    for (int k = m.dofact_adr[i]; k < m.dofact_adr[i + 1]; k++) { int a = m.dofact_act[k]; s += MJB_PRM_REC(PRM_ACT_GEAR, c, m, actuator_gear, 6, 6 * m.nu, a, 0) * af[a]; }
     for (int k = 0; k < m.nsiteact; k++) {
-      int a = m.siteact[k], id = m.actuator_trnid[2 * a], b = m.site_bodyid[id];
+      int a = m.siteact[k], id = MJB_REC(m, actuator_trnid, 2, a, 0), b = m.site_bodyid[id];
       if (!((m.body_dofmask[b] >> i) & 1ull)) continue;
       T g[6], R[9], f[3], tq[3], pt[3] = {sx[3 * id], sx[3 * id + 1], sx[3 * id + 2]}, jp[3], jr[3];
 #pragma unroll
-      for (int q = 0; q < 6; q++) g[q] = gear[6 * a + q];
+      for (int q = 0; q < 6; q++) g[q] = MJB_PRM_REC(PRM_ACT_GEAR, c, m, actuator_gear, 6, 6 * m.nu, a, q);
 #pragma unroll
       for (int q = 0; q < 9; q++) R[q] = sm[9 * id + q];
       mulmatvec3(f, R, g);
@@ -2555,8 +2614,8 @@ template <typename T, int G> MJB_DEV void forward(Ctx<T>& c) {
 // A16 position integration for the joints of one environment (lanes over joints)
 template <typename T, int G> MJB_DEV void integrate_pos(ModelRef<T> m, T* qpos, const T* qvel, T h, int lane) {
   for (int j = lane; j < m.njnt; j += G) {
-    int qa = m.jnt_irec[6 * j + 1], da = m.jnt_irec[6 * j + 2];
-    if (m.jnt_irec[6 * j] == JNT_FREE) {
+    int qa = MJB_REC(m, jnt_irec, 6, j, 1), da = MJB_REC(m, jnt_irec, 6, j, 2);
+    if (MJB_REC(m, jnt_irec, 6, j, 0) == JNT_FREE) {
       qpos[qa] += h * qvel[da]; qpos[qa + 1] += h * qvel[da + 1]; qpos[qa + 2] += h * qvel[da + 2];
       T q[4] = {qpos[qa + 3], qpos[qa + 4], qpos[qa + 5], qpos[qa + 6]}, wv[3] = {qvel[da + 3], qvel[da + 4], qvel[da + 5]};
       quat_integrate(q, wv, h);
@@ -2644,7 +2703,7 @@ template <typename T, int G> MJB_DEV void random_ctrl(ModelRef<T> m, T* ctrl, un
     unsigned r = philox_first(env, step, (unsigned)a, 0u, seed, 0x5EEDu);
     T u = (T)(r >> 8) * (T)(1.0 / 16777216.0);
     T lo = -1, hi = 1;
-    if (m.actuator_ctrllimited[a]) { lo = m.actuator_ctrlrange[2 * a]; hi = m.actuator_ctrlrange[2 * a + 1]; }
+    if (m.actuator_ctrllimited[a]) { lo = MJB_REC(m, actuator_ctrlrange, 2, a, 0); hi = MJB_REC(m, actuator_ctrlrange, 2, a, 1); }
     ctrl[a] = (T)0.5 * (lo + hi) + (T)0.5 * (hi - lo) * scale * (2 * u - 1);
   }
 }
@@ -2674,7 +2733,7 @@ template <typename T, int G> MJB_DEV void feedback_ctrl(Ctx<T>& c, ArgsRef a, un
       const long idx = ((long)step + (long)env * a.fb_env_stride) % a.fb_nsteps;
       u += ((const T MJB_CONST*)a.fb_noise_std)[act] * ((const T MJB_CONST*)a.fb_noise_tab)[idx * nu + act];
     }
-    if (m.actuator_ctrllimited[act]) u = t_min(t_max(u, m.actuator_ctrlrange[2 * act]), m.actuator_ctrlrange[2 * act + 1]);
+    if (m.actuator_ctrllimited[act]) u = t_min(t_max(u, MJB_REC(m, actuator_ctrlrange, 2, act, 0)), MJB_REC(m, actuator_ctrlrange, 2, act, 1));
     ctrl[act] = u;
   }
   gsync<G>();

@@ -206,6 +206,14 @@ struct HostModel {
 
 // Fill DevModel<T> through an allocator that returns pointers valid where the kernels run.
 //   alloc.putf(const std::vector<T>&) -> const T*;  alloc.puti(...) -> const int*;  alloc.putu(...) -> const unsigned long long*
+// A table of records is put with its record stride (values per record) as a second argument where the allocator takes one (the
+// allocator that emits the baked model of a specialised kernel: it looks for uniform columns); every other allocator ignores it.
+namespace put_detail {
+template <typename A, typename V> auto f(A& a, const V& v, int stride, int) -> decltype(a.putf(v, stride)) { return a.putf(v, stride); }
+template <typename A, typename V> auto f(A& a, const V& v, int, long) -> decltype(a.putf(v)) { return a.putf(v); }
+template <typename A, typename V> auto i(A& a, const V& v, int stride, int) -> decltype(a.puti(v, stride)) { return a.puti(v, stride); }
+template <typename A, typename V> auto i(A& a, const V& v, int, long) -> decltype(a.puti(v)) { return a.puti(v); }
+}  // namespace put_detail
 template <typename T, typename Alloc>
 void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max, DevModel<T>& m) {
   std::memset((void*)&m, 0, sizeof(m));
@@ -222,37 +230,38 @@ void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max
   typedef typename DevModel<T>::FP FP;
   typedef typename DevModel<T>::IP IP;
   typedef typename DevModel<T>::UP UP;
-  auto F = [&](const char* k) -> FP {
+  // (record strides: the [n, k] shapes of the compiled model's arrays)
+  auto F = [&](const char* k, int stride = 1) -> FP {
     const auto& v = h.D(k);
     std::vector<T> tv(v.begin(), v.end());
-    return (FP)alloc.putf(tv);
+    return (FP)put_detail::f(alloc, tv, stride, 0);
   };
-  auto Iq = [&](const char* k) -> IP { return (IP)alloc.puti(h.I(k)); };
+  auto Iq = [&](const char* k, int stride = 1) -> IP { return (IP)put_detail::i(alloc, h.I(k), stride, 0); };
   m.body_parentid = Iq("body_parentid"); m.body_depth = Iq("body_depth"); m.body_round = (IP)alloc.puti(h.body_round); m.nround = h.nround; m.nround_inner = h.nround_inner;
   m.body_nsub = (IP)alloc.puti(h.body_nsub); m.body_anc = (IP)alloc.puti(h.body_anc); m.max_nsub = h.max_nsub; m.dfs_ok = h.dfs_ok; m.body_rootid = Iq("body_rootid"); m.body_jntadr = Iq("body_jntadr"); m.body_jntnum = Iq("body_jntnum");
   m.body_dofadr = Iq("body_dofadr"); m.body_dofnum = Iq("body_dofnum");
   m.level_adr = (IP)alloc.puti(h.level_adr); m.level_body = (IP)alloc.puti(h.level_body); m.child_adr = (IP)alloc.puti(h.child_adr); m.child_id = (IP)alloc.puti(h.child_id); m.tri_tab = (IP)alloc.puti(h.tri_tab);
   m.dofact_adr = (IP)alloc.puti(h.dofact_adr); m.dofact_act = (IP)alloc.puti(h.dofact_act); m.siteact = (IP)alloc.puti(h.siteact); m.mpair = (IP)alloc.puti(h.mpair);
-  m.body_pos = F("body_pos"); m.body_quat = F("body_quat"); m.body_ipos = F("body_ipos"); m.body_iquat = F("body_iquat"); m.body_mass = F("body_mass");
-  m.body_inertia = F("body_inertia"); m.body_subtreemass = F("body_subtreemass"); m.body_invweight0 = F("body_invweight0");
+  m.body_pos = F("body_pos", 3); m.body_quat = F("body_quat", 4); m.body_ipos = F("body_ipos", 3); m.body_iquat = F("body_iquat", 4); m.body_mass = F("body_mass");
+  m.body_inertia = F("body_inertia", 3); m.body_subtreemass = F("body_subtreemass"); m.body_invweight0 = F("body_invweight0", 2);
   m.body_dofmask = (UP)alloc.putu(h.body_dofmask); m.dof_ancmask = (UP)alloc.putu(h.dof_ancmask);
   m.jnt_type = Iq("jnt_type"); m.jnt_qposadr = Iq("jnt_qposadr"); m.jnt_dofadr = Iq("jnt_dofadr"); m.jnt_bodyid = Iq("jnt_bodyid"); m.jnt_limited = Iq("jnt_limited");
-  m.jnt_pos = F("jnt_pos"); m.jnt_axis = F("jnt_axis"); m.jnt_range = F("jnt_range"); m.jnt_stiffness = F("jnt_stiffness"); m.jnt_margin = F("jnt_margin");
-  m.jnt_solref = F("jnt_solref"); m.jnt_solimp = F("jnt_solimp"); m.qpos0 = F("qpos0"); m.qpos_spring = F("qpos_spring");
+  m.jnt_pos = F("jnt_pos", 3); m.jnt_axis = F("jnt_axis", 3); m.jnt_range = F("jnt_range", 2); m.jnt_stiffness = F("jnt_stiffness"); m.jnt_margin = F("jnt_margin");
+  m.jnt_solref = F("jnt_solref", 2); m.jnt_solimp = F("jnt_solimp", 5); m.qpos0 = F("qpos0"); m.qpos_spring = F("qpos_spring");
   m.dof_bodyid = Iq("dof_bodyid"); m.dof_jntid = Iq("dof_jntid"); m.dof_parentid = Iq("dof_parentid");
   m.dof_armature = F("dof_armature"); m.dof_damping = F("dof_damping"); m.dof_invweight0 = F("dof_invweight0");
-  m.geom_type = Iq("geom_type"); m.geom_bodyid = Iq("geom_bodyid"); m.geom_pos = F("geom_pos"); m.geom_quat = F("geom_quat"); m.geom_size = F("geom_size");
-  m.site_bodyid = Iq("site_bodyid"); m.site_pos = F("site_pos"); m.site_quat = F("site_quat");
+  m.geom_type = Iq("geom_type"); m.geom_bodyid = Iq("geom_bodyid"); m.geom_pos = F("geom_pos", 3); m.geom_quat = F("geom_quat", 4); m.geom_size = F("geom_size", 3);
+  m.site_bodyid = Iq("site_bodyid"); m.site_pos = F("site_pos", 3); m.site_quat = F("site_quat", 4);
   m.tendon_adr = Iq("tendon_adr"); m.tendon_num = Iq("tendon_num"); m.tendon_limited = Iq("tendon_limited"); m.wrap_objid = Iq("wrap_objid");
-  m.tendon_range = F("tendon_range"); m.tendon_margin = F("tendon_margin"); m.tendon_solref = F("tendon_solref"); m.tendon_solimp = F("tendon_solimp");
+  m.tendon_range = F("tendon_range", 2); m.tendon_margin = F("tendon_margin"); m.tendon_solref = F("tendon_solref", 2); m.tendon_solimp = F("tendon_solimp", 5);
   m.tendon_invweight0 = F("tendon_invweight0"); m.wrap_prm = F("wrap_prm");
-  m.actuator_trntype = Iq("actuator_trntype"); m.actuator_trnid = Iq("actuator_trnid"); m.actuator_biastype = Iq("actuator_biastype");
+  m.actuator_trntype = Iq("actuator_trntype"); m.actuator_trnid = Iq("actuator_trnid", 2); m.actuator_biastype = Iq("actuator_biastype");
   m.actuator_ctrllimited = Iq("actuator_ctrllimited"); m.actuator_forcelimited = Iq("actuator_forcelimited"); m.actuator_group = Iq("actuator_group");
-  m.actuator_gear = F("actuator_gear"); m.actuator_gainprm = F("actuator_gainprm"); m.actuator_biasprm = F("actuator_biasprm");
-  m.actuator_ctrlrange = F("actuator_ctrlrange"); m.actuator_forcerange = F("actuator_forcerange");
+  m.actuator_gear = F("actuator_gear", 6); m.actuator_gainprm = F("actuator_gainprm", 3); m.actuator_biasprm = F("actuator_biasprm", 3);
+  m.actuator_ctrlrange = F("actuator_ctrlrange", 2); m.actuator_forcerange = F("actuator_forcerange", 2);
   m.sensor_type = Iq("sensor_type"); m.sensor_objid = Iq("sensor_objid"); m.sensor_adr = Iq("sensor_adr");
   m.pair_geom1 = Iq("pair_geom1"); m.pair_geom2 = Iq("pair_geom2"); m.pair_condim = Iq("pair_condim");
-  m.pair_friction = F("pair_friction"); m.pair_solref = F("pair_solref"); m.pair_solimp = F("pair_solimp"); m.pair_margin = F("pair_margin"); m.pair_gap = F("pair_gap");
+  m.pair_friction = F("pair_friction", 5); m.pair_solref = F("pair_solref", 2); m.pair_solimp = F("pair_solimp", 5); m.pair_margin = F("pair_margin"); m.pair_gap = F("pair_gap");
   {
     // constraint-row constants folded on the host: K, B of a row depend only on solref, solimp[1] and the timestep
     const double MINIMP = 0.0001, MAXIMP = 0.9999, MINVAL = 1e-15;
@@ -289,10 +298,10 @@ void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max
       r[2] = (T)K; r[3] = (T)B;
       clamp_solimp(&psi[5 * p], r + 4);
     }
-    m.pair_kb = (FP)alloc.putf(kb);
+    m.pair_kb = (FP)put_detail::f(alloc, kb, PAIR_KB_STRIDE, 0);
     std::vector<int> pb((size_t)h.npair * 2);
     for (int p = 0; p < h.npair; p++) { pb[2 * p] = gb[g1[p]]; pb[2 * p + 1] = gb[g2[p]]; }
-    m.pair_body = (IP)alloc.puti(pb);
+    m.pair_body = (IP)put_detail::i(alloc, pb, 2, 0);
     const int nobj = h.njnt + h.ntendon;
     std::vector<T> lf((size_t)nobj * 12, (T)0);
     std::vector<int> li((size_t)nobj * 2, 0);
@@ -319,8 +328,8 @@ void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max
         li[2 * (h.njnt + t)] = tl[t] != 0 ? 1 : 0; li[2 * (h.njnt + t) + 1] = t;
       }
     }
-    m.lim_f = (FP)alloc.putf(lf);
-    m.lim_i = (IP)alloc.puti(li);
+    m.lim_f = (FP)put_detail::f(alloc, lf, 12, 0);
+    m.lim_i = (IP)put_detail::i(alloc, li, 2, 0);
     // kinematics records
     const auto& jp = h.D("jnt_pos"); const auto& ja = h.D("jnt_axis"); const auto& q0 = h.D("qpos0");
     std::vector<T> jrec((size_t)h.njnt * 8, (T)0);
@@ -346,12 +355,12 @@ void fill_dev_model(const HostModel& h, Alloc& alloc, int ncon_max, int nefc_max
         r[4] = spring ? jq[j] : -1;
         dfr[4 * i] = (T)dd[i]; dfr[4 * i + 1] = (T)(spring ? js[j] : 0.0); dfr[4 * i + 2] = (T)(spring ? qs[jq[j]] : 0.0);
       }
-      m.dof_irec = (IP)alloc.puti(dir); m.dof_frec = (FP)alloc.putf(dfr);
+      m.dof_irec = (IP)put_detail::i(alloc, dir, 6, 0); m.dof_frec = (FP)put_detail::f(alloc, dfr, 4, 0);
     }
     const auto& bja = h.I("body_jntadr"); const auto& bjn = h.I("body_jntnum");
     std::vector<int> birec((size_t)h.nbody * 4, 0);
     for (int b = 0; b < h.nbody; b++) { birec[4 * b] = bja[b]; birec[4 * b + 1] = bjn[b]; birec[4 * b + 2] = bjn[b] > 0 ? jt[bja[b]] : -1; }
-    m.jnt_rec = (FP)alloc.putf(jrec); m.jnt_irec = (IP)alloc.puti(jirec); m.body_irec = (IP)alloc.puti(birec);
+    m.jnt_rec = (FP)put_detail::f(alloc, jrec, 8, 0); m.jnt_irec = (IP)put_detail::i(alloc, jirec, 6, 0); m.body_irec = (IP)put_detail::i(alloc, birec, 4, 0);
   }
   {
     // bounding radius of every geom about its centre (conservative), folded with the pair margin for the broad phase

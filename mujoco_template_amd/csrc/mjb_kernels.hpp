@@ -241,7 +241,7 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
         } else {
           const int a = k - 2 * nv;
           const T v = w[L.ctrl + a] + sgn * eps;
-          if (m.actuator_ctrllimited[a] && (v < m.actuator_ctrlrange[2 * a] || v > m.actuator_ctrlrange[2 * a + 1])) ok = 0;
+          if (m.actuator_ctrllimited[a] && (v < MJB_REC(m, actuator_ctrlrange, 2, a, 0) || v > MJB_REC(m, actuator_ctrlrange, 2, a, 1))) ok = 0;
           gsync<G>();
           if (lane == 0 && ok) w[L.ctrl + a] = v;
         }

@@ -99,6 +99,12 @@ struct Lay {
   int bytes;          // total bytes per environment (rounded to 16)
 };
 
+// Uniform record columns of a baked model (specialised translation units, baked_model_source in mjb_api.hip).  W is the index of a
+// table's pointer among the 8-byte words of DevModel<T> (offsetof / 8).  For a table of records whose column k holds the same bits
+// in every record, the generated translation unit specialises this with bit k of `mask` set and val[k] = that value; MJB_REC
+// (mjb_device.hpp) then reads the constant instead of the table.  Everywhere else the mask is 0 and a record read is a table read.
+template <int W> struct UniformCols { static constexpr unsigned long long mask = 0; };
+
 constexpr int PAIR_KB_STRIDE = 12;
 constexpr int CON_STRIDE = 11;  // dist, pos[3], normal[3], tangent1[3], mu (friction[0]); tangent2 = n x t1; pair id in i_con_pair
 
