@@ -563,6 +563,52 @@ typedef struct mjbTrajSelect {
 } mjbTrajSelect;
 int mjb_traj_select(mjbData* d, const mjbTrajSelect* p);
 
+/* ---- the equilibrium controls of a batch of operating points: the minimum-norm u of
+ *   min_u | u @ moment - qfrc |_2,     moment [nu, nv] the actuator moment matrix,  qfrc [nv] the force inverse dynamics asks for,
+ * with the singular values of moment and a conditioning verdict per problem.  It is the head of the reference's controller design,
+ * ctrl0 = qfrc0 @ pinv(actuator_moment) behind an SVD guard against a singular moment matrix (mujoco_template/setpoints.py:50-51,
+ * examples/humanoid/controllers/lqr.py:83): ctrl0 is both the point mjb_transition_fd_points linearises at and the u0 of the feedback
+ * law.  mjb_inverse leaves qfrc_inverse [batch, nv] and actuator_moment [batch, nu, nv] in device memory; this call reads them there.
+ * One-sided (Hestenes) Jacobi SVD of G = moment' itself - never an eigen-solve of G'G, which would square the condition number the
+ * guard tests; Jacobi also keeps high relative accuracy when actuator rows differ by orders of magnitude (gear ratios).  Per problem
+ * e, in float64, float32 inputs widened exactly:
+ *   1. G [nv, nu], column a = row a of moment; V = I [nu, nu].  An entry of moment or qfrc that is not finite ends with status 1, and so
+ *      does a float64 sum(G^2) that is not finite (finite entries above 1e154, whose squares overflow: no norm can be formed).
+ *   2. tol = 2^-52, floor = tol^2 * sum(G^2): a column whose squared norm is <= floor is rounding noise and is never rotated (without
+ *      this nu > nv never converges).
+ *   3. Sweeps of a fixed round-robin schedule: n' = nu rounded up to even, n' - 1 rounds of n' / 2 disjoint pairs (round rd: pair 0 =
+ *      (n' - 1, rd), pair k = ((rd + k) mod (n' - 1), (rd - k) mod (n' - 1)); a pair with an index >= nu is idle); the pairs of a
+ *      round run concurrently.  For a pair i < j: a = |g_i|^2, b = |g_j|^2, c = g_i . g_j; skipped if c == 0 or
+ *      |c| <= tol sqrt(a) sqrt(b) or min(a, b) <= floor; otherwise z = (b - a) / (2 c), t = sign(z) / (|z| + hypot(1, z)) (z == 0:
+ *      t = 1), cs = 1 / sqrt(1 + t^2), sn = cs t, (g_i, g_j) <- (cs g_i - sn g_j, sn g_i + cs g_j) and the same for V.
+ *   4. A sweep without a rotation ends the iteration (it counts in sweeps); max_sweeps sweeps that each rotated something end with
+ *      status 2.  max_sweeps: 0 = the default of 30, else 1 .. 64.
+ *   5. sigma_j = sqrt(|g_j|^2), sorted descending, ties by lower index; r = min(nu, nv); sv = the first r; rcond = sigma_r / sigma_1
+ *      (0 when sigma_1 == 0); rank = the count of sigma_j > rcond_min * sigma_1 among them; rcond < rcond_min ends with status 3 - the
+ *      reference's TemplateError("... singular or ill-conditioned"), reported per environment instead of raised.
+ *   6. ctrl = sum_j v_j (g_j . qfrc) / sigma_j^2 over the first r columns in sorted order (terms with sigma_j == 0 skipped);
+ *      residual = max_i |(ctrl @ moment - qfrc)_i|, moment re-read from global memory: the force no actuator can supply (a free root);
+ *      pinv [nv, nu] = sum_j g_j v_j' / sigma_j^2, the shape and meaning of numpy.linalg.pinv(moment).  Every reduction runs in a fixed order.
+ * Inputs: moment [nu, nv], qfrc [nv] per problem e at ptr + e * env_stride (step_stride ignored; env_stride 0 = shared by all
+ * problems), MJB_F32 or MJB_F64 each.  1 <= nu <= 32, 1 <= nv <= 64; batch is the call's own, not the data object's; rcond_min >= 0 and
+ * finite (the reference's guard is 1e-12).
+ * Outputs, dense: ctrl [batch, nu], sv [batch, min(nu, nv)], rcond [batch], residual [batch], pinv [batch, nv, nu] (NULL = not
+ * wanted); rank, sweeps, status [batch] int32.  For a non-zero status ctrl[e] and pinv[e] are NaN and residual[e] is +inf (the
+ * convention of mjb_lqr_eig / mjb_lqr_dlyap: a failed set-point cannot be applied silently); sv, rcond, rank and sweeps hold what was
+ * reached (status 1: NaN, NaN, 0, 0); no other problem is affected.  A problem's results are bitwise the same at any position of any batch.
+ * Checks, launch and stream as mjb_lqr_dlyap (MJB_ERR_ARG with a message before anything is launched, outputs untouched): sizes,
+ * rcond_min, strides >= 0, required pointers, device memory of the data's device, the highest element inside its allocation; ONE
+ * kernel launch on the data's stream (one wavefront per problem, G and V resident in LDS), no scratch memory, no allocation, no host
+ * copy, no synchronisation. */
+typedef struct mjbSetpoint {
+  int batch, nu, nv, max_sweeps;
+  double rcond_min;
+  mjbStridedIn moment, qfrc;
+  double *ctrl, *sv, *rcond, *residual, *pinv;
+  int *rank, *sweeps, *status;
+} mjbSetpoint;
+int mjb_setpoint_ctrl(mjbData* d, const mjbSetpoint* p);
+
 /* ---- mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacSubtreeCom (reference jacobians.py:44-79).
  * kinds[i]: 0 site, 1 body, 2 bodycom, 3 subtreecom.  jacp/jacr host [batch, nreq, 3, nv] float64 (jacr may be NULL) ---- */
 int mjb_jac(mjbData* d, int nreq, const int* kinds, const int* ids, double* jacp_host, double* jacr_host);

@@ -95,6 +95,13 @@ class TrajCostStruct(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("cost", "cost_t", "lx", "lu", "VxT")]
 
 
+class SetpointStruct(ctypes.Structure):
+    """``mjbSetpoint`` (include/mjbatch.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("batch", "nu", "nv", "max_sweeps")] + [("rcond_min", ctypes.c_double)] + \
+               [(n, StridedIn) for n in ("moment", "qfrc")] + \
+               [(n, ctypes.c_void_p) for n in ("ctrl", "sv", "rcond", "residual", "pinv", "rank", "sweeps", "status")]
+
+
 class TrajSelectStruct(ctypes.Structure):
     """``mjbTrajSelect`` (include/mjbatch.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("nprob", "ncand", "T", "nu", "mode", "cand_dtype", "out_dtype")] + \
@@ -183,6 +190,8 @@ def load_library() -> ctypes.CDLL:
     L.mjb_lqr_eig.restype = ci
     L.mjb_lqr_dlyap.argtypes = [vp, ctypes.POINTER(LqrDlyapStruct)]
     L.mjb_lqr_dlyap.restype = ci
+    L.mjb_setpoint_ctrl.argtypes = [vp, ctypes.POINTER(SetpointStruct)]
+    L.mjb_setpoint_ctrl.restype = ci
     L.mjb_lqr_gemm_tn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.mjb_lqr_gemm_tn.restype = ci
     L.mjb_traj_cost.argtypes = [vp, ctypes.POINTER(TrajCostStruct)]
@@ -1101,6 +1110,14 @@ class BatchSim:
         struct = LqrDlyapStruct()
         struct.tol = float(sizes["tol"])
         self._lqr_call(load_library().mjb_lqr_dlyap, struct, {k: v for k, v in sizes.items() if k != "tol"}, arrays, pointers, keep)
+
+    def setpoint_ctrl(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
+        """``mjb_setpoint_ctrl`` on raw device addresses (see ``lqr_backward``): ``sizes`` batch, nu, nv, max_sweeps (0 = the default),
+        rcond_min; ``arrays`` moment, qfrc as (address, 0, env stride, dtype code: 0 float32, 1 float64); ``pointers`` ctrl, sv, rcond,
+        residual, pinv (0 = not wanted), rank, sweeps, status.  ``setpoints.solve_setpoint`` is the checked tensor interface on top of it."""
+        struct = SetpointStruct()
+        struct.rcond_min = float(sizes["rcond_min"])
+        self._lqr_call(load_library().mjb_setpoint_ctrl, struct, {k: v for k, v in sizes.items() if k != "rcond_min"}, arrays, pointers, keep)
 
     def traj_cost(self, sizes: dict, arrays: dict, pointers: dict, keep=()) -> None:
         """``mjb_traj_cost`` on raw device addresses (see ``lqr_backward``); the state and control entries of ``arrays`` carry a

@@ -23,6 +23,7 @@
 #include "mjb_dare.hpp"
 #include "mjb_eig.hpp"
 #include "mjb_dlyap.hpp"
+#include "mjb_setpoint.hpp"
 #include "mjb_traj.hpp"
 
 using namespace mjb;
@@ -1871,6 +1872,41 @@ int mjb_lqr_dlyap(mjbData* d, const mjbLqrDlyap* p) {
   a.P = p->P; a.J = p->J; a.change = p->change; a.iters = p->iters; a.status = p->status;
   const hipError_t e = dlyap_launch(a, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_lqr_dlyap launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+// ---- mjb_setpoint_ctrl: the checks (those of mjb_lqr_dlyap); the kernel and its launch are in mjb_setpoint.hip ----
+int mjb_setpoint_ctrl(mjbData* d, const mjbSetpoint* p) {
+  static const char* fn = "mjb_setpoint_ctrl";
+  if (!d || !p) return fail(MJB_ERR_ARG, "mjb_setpoint_ctrl: NULL argument");
+  static const char* const msg[7] = {"", ": batch must be >= 1", ": nu must lie in [1, 32]", ": nv must lie in [1, 64] (the matrix the kernel keeps in LDS)",
+                                     ": max_sweeps must be 0 (the default, 30) or lie in [1, 64]", ": rcond_min must be finite and >= 0",
+                                     ": batch * nu * nv is too large"};
+  const int why = setpoint_size_error(p->batch, p->nu, p->nv, p->max_sweeps, p->rcond_min);
+  if (why) return fail(MJB_ERR_ARG, std::string(fn) + msg[why]);
+  if ((p->moment.dtype != MJB_F32 && p->moment.dtype != MJB_F64) || (p->qfrc.dtype != MJB_F32 && p->qfrc.dtype != MJB_F64))
+    return fail(MJB_ERR_ARG, "mjb_setpoint_ctrl: the dtype of moment and of qfrc must be MJB_F32 or MJB_F64");
+  HIPCHK(hipSetDevice(d->device));
+  const long B = p->batch, nu = p->nu, nv = p->nv, r = nu < nv ? nu : nv;
+  int rc;
+  if ((rc = check_lqr_array(d, fn, "moment", p->moment.ptr, false, 1, B, nu * nv, 0, p->moment.env_stride, p->moment.dtype == MJB_F32 ? 4 : 8)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "qfrc", p->qfrc.ptr, false, 1, B, nv, 0, p->qfrc.env_stride, p->qfrc.dtype == MJB_F32 ? 4 : 8)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "ctrl", p->ctrl, false, 1, B, nu, 0, nu)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "sv", p->sv, false, 1, B, r, 0, r)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "rcond", p->rcond, false, 1, B, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "residual", p->residual, false, 1, B, 1, 0, 1)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "pinv", p->pinv, true, 1, B, nv * nu, 0, nv * nu)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "rank", p->rank, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "sweeps", p->sweeps, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_lqr_array(d, fn, "status", p->status, false, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  SetpointArgs a;
+  a.B = p->batch; a.nu = p->nu; a.nv = p->nv; a.max_sweeps = p->max_sweeps; a.rcond_min = p->rcond_min;
+  a.m_f32 = p->moment.dtype == MJB_F32; a.q_f32 = p->qfrc.dtype == MJB_F32;
+  a.moment = p->moment.ptr; a.qfrc = p->qfrc.ptr; a.m_es = p->moment.env_stride; a.q_es = p->qfrc.env_stride;
+  a.ctrl = p->ctrl; a.sv = p->sv; a.rcond = p->rcond; a.residual = p->residual; a.pinv = p->pinv;
+  a.rank = p->rank; a.sweeps = p->sweeps; a.status = p->status;
+  const hipError_t e = setpoint_launch(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_setpoint_ctrl launch: ") + hipGetErrorString(e));
   return MJB_OK;
 }
 
