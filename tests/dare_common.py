@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from tests.lqr_common import FLOOR, FLOOR_DARE, _chol_solve, bound, generate, rel_err  # noqa: F401  (re-exported)
+from tests.lqr_common import EDGE_SIZES, FLOOR, FLOOR_DARE, _chol_solve, bound, generate, rel_err  # noqa: F401  (re-exported)
 
 TOL, MAX_ITER = 1e-12, 32
 TRUTH_TOL, TRUTH_MAX_ITER = 1e-17, 64
@@ -151,7 +151,8 @@ def humanoid_case(scales=(1.0,)):
 
 CASES = [(f"gen{nx}x{nu}", lambda n, nx=nx, nu=nu: generator_case(nx, nu, n)) for nx, nu in GENERATOR_SIZES] + \
         [(f"mech{nx}x{nu}", lambda n, nx=nx, nu=nu: mechanical_case(nx, nu, n)) for nx, nu in MECHANICAL_SIZES] + \
-        [("zerocol7x3", lambda n: zero_column_case(n))]
+        [("zerocol7x3", lambda n: zero_column_case(n))] + \
+        [(f"gen{nx}x{nu}", lambda n, nx=nx, nu=nu: generator_case(nx, nu, n)) for nx, nu in EDGE_SIZES]     # the edges of the launch dispatch
 
 
 def judge(case, got, label, record=None):

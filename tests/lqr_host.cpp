@@ -52,6 +52,7 @@ int lqrh_highest_element(long T, long B, long n, long ss, long es, long long* hi
   return 0;
 }
 int lqrh_size_error(long T, long B, long nx, long nu) { return lqr_size_error(T, B, nx, nu); }
+int lqrh_waves(int nx) { return lqr_waves(nx); }
 long lqrh_lds_bytes(int nx, int nu) { return (long)lqr_layout(nx, nu).total * 8; }
 long lqrh_cand_lds_bytes(int nx, int nu, int nalpha) { return (long)lqr_cand_layout(nx, nu, nalpha).total * 8; }
 // 1 when no two arrays that are live in the same half of a step overlap and everything lies inside `total`

@@ -99,6 +99,19 @@ def test_failures_are_reported_not_propagated(driver):
     dc.check_statuses(lambda case, max_iter: host_dare(driver, case, max_iter=max_iter), "host")
 
 
+def test_results_do_not_depend_on_the_batch_position(driver):
+    """(16, 9), the <1, 32> variant: five systems in one launch against each system launched alone, every output bit for bit.  The
+    emulation runs the systems one after the other in the SAME LDS buffer, so a read of LDS that the system itself has not written
+    would show here."""
+    case = dc.generator_case(16, 9, 5)
+    got = host_dare(driver, case)
+    assert got["status"].tolist() == [0] * 5
+    for e in range(5):
+        alone = host_dare(driver, {k: v[e:e + 1] for k, v in case.items()})
+        for key in ("X", "K", "change", "iters", "status"):
+            assert np.array_equal(got[key][e:e + 1], alone[key]), (e, key)
+
+
 # ---- 3. layout --------------------------------------------------------------------------------------------------------------------------
 def test_size_limits_and_lds_layout(driver):
     ok = driver.dareh_size_error
@@ -106,11 +119,12 @@ def test_size_limits_and_lds_layout(driver):
     assert ok(0, 4, 1, 32, 1e-12) == 1 and ok(1, 65, 1, 32, 1e-12) == 2 and ok(1, 0, 1, 32, 1e-12) == 2 and ok(1, 4, 33, 32, 1e-12) == 3
     assert ok(1, 4, 0, 32, 1e-12) == 3 and ok(1, 4, 1, 0, 1e-12) == 4 and ok(1, 4, 1, 65, 1e-12) == 4
     assert ok(1, 4, 1, 32, -1e-12) == 5 and ok(1, 4, 1, 32, float("nan")) == 5
-    for nx in (1, 2, 4, 7, 16, 17, 54, 64):
+    sizes = [(nx, nu) for nx in (1, 2, 4, 7, 16, 17, 54, 64) for nu in (1, 3, 8, 9, 21, 32)]
+    for nx, nu in sizes + [s for s in dc.EDGE_SIZES if s not in sizes]:
         assert driver.dareh_packed_roundtrip(nx) == 1, nx
-        for nu in (1, 3, 8, 9, 21, 32):
-            assert driver.dareh_layout_ok(nx, nu) == 1, (nx, nu)
-            assert driver.dareh_lds_bytes(nx, nu) <= 160 * 1024, (nx, nu)
+        assert ok(1, nx, nu, 32, 1e-12) == 0, (nx, nu)
+        assert driver.dareh_layout_ok(nx, nu) == 1, (nx, nu)
+        assert driver.dareh_lds_bytes(nx, nu) <= 160 * 1024, (nx, nu)
     assert driver.dareh_lds_bytes(4, 1) < 2048                  # the cart-pole: many workgroups per compute unit
 
 

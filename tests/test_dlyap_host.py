@@ -100,7 +100,7 @@ def test_humanoid_policy_evaluation_is_the_dare_solution(driver):
     assert mine <= lc.bound(np64, lc.FLOOR_DARE), (mine, np64)
 
 
-@pytest.mark.parametrize("nx,nu", [(12, 4), (17, 5)])
+@pytest.mark.parametrize("nx,nu", [(12, 4), (17, 5), (16, 9), (3, 9)])
 def test_gramian_form_matches_the_restatement_and_scipy(driver, nx, nu):
     """transpose: P = M P M' + S (12-14 iterations), against the restatement and scipy.linalg.solve_discrete_lyapunov(M, S)."""
     from scipy.linalg import solve_discrete_lyapunov
@@ -147,6 +147,18 @@ def test_failures_are_reported_not_propagated(driver):
     lc.check_statuses(lambda case, max_iter: host_dlyap(driver, case, max_iter=max_iter), "host")
 
 
+def test_results_do_not_depend_on_the_batch_position(driver):
+    """(16, 9), the largest one-wave state: five systems in one launch against each system launched alone, every output bit for bit
+    (the emulation runs them one after the other in the SAME LDS buffer)."""
+    case = lc.gain_case("gen16x9", lambda n: dc.generator_case(16, 9, n), 5)
+    got = host_dlyap(driver, case)
+    assert got["status"].tolist() == [0] * 5
+    for e in range(5):
+        alone = host_dlyap(driver, {k: v[e:e + 1] for k, v in case.items()})
+        for key in ("P", "J", "change", "iters", "status"):
+            assert np.array_equal(got[key][e:e + 1], alone[key]), (e, key)
+
+
 def test_near_marginal_system_converges(driver):
     """M = [[1 - 1e-9, 1], [0, 0.5]], Q = I: rho = 1 - 1e-9 converges, at iteration 35."""
     case = {"A": np.array([[[1.0 - 1e-9, 1.0], [0.0, 0.5]]]), "Q": np.eye(2)[None]}
@@ -168,10 +180,11 @@ def test_size_limits_and_lds_layout(driver):
     assert ok(1, 4, 1, 1, 64, -1e-12, -1) == 5 and ok(1, 4, 1, 1, 64, float("nan"), -1) == 5
     assert ok(1, 4, 1, 1, 64, 1e-12, 0) == 6 and ok(1, 4, 1, 1, 64, 1e-12, 2) == 6
     assert ok(1 << 30, 64, 1, 1, 64, 1e-12, -1) == 7
-    for nx in (1, 2, 4, 7, 16, 17, 54, 64):
-        for nu in (0, 1, 3, 8, 9, 21, 32):
-            assert driver.dlyaph_layout_ok(nx, nu) == 1, (nx, nu)
-            assert driver.dlyaph_lds_bytes(nx, nu) <= 160 * 1024, (nx, nu)
+    sizes = [(nx, nu) for nx in (1, 2, 4, 7, 16, 17, 54, 64) for nu in (0, 1, 3, 8, 9, 21, 32)]
+    for nx, nu in sizes + [s for s in dc.EDGE_SIZES if s not in sizes]:
+        assert ok(1, nx, nu, int(nu > 0), 64, 1e-12, -1) == 0, (nx, nu)
+        assert driver.dlyaph_layout_ok(nx, nu) == 1, (nx, nu)
+        assert driver.dlyaph_lds_bytes(nx, nu) <= 160 * 1024, (nx, nu)
     assert driver.dlyaph_lds_bytes(4, 1) < 2048                  # the cart-pole: many workgroups per compute unit
 
 

@@ -108,6 +108,20 @@ def test_failures_are_reported_not_propagated(ctx):
     dc.check_statuses(lambda case, max_iter: _np(mt.solve_dare(data, *(_dev(torch, case[k]) for k in "ABQR"), max_iter=max_iter)), "gpu")
 
 
+def test_results_do_not_depend_on_the_batch_position(ctx):
+    """(16, 9), k_lqr_dare<1, 32>: five systems in one launch against each system launched alone, every output bit for bit."""
+    import mujoco_template_amd as mt
+
+    torch, _, data = ctx
+    case = _case("gen16x9", lambda n: dc.generator_case(16, 9, n))
+    got = _np(mt.solve_dare(data, *(_dev(torch, case[k]) for k in "ABQR")))
+    assert got["status"].tolist() == [0] * NB and np.abs(got["K"]).max() > 0
+    for e in range(NB):
+        alone = _np(mt.solve_dare(data, *(_dev(torch, case[k][e:e + 1]) for k in "ABQR")))
+        for key in ("X", "K", "change", "iters", "status"):
+            assert np.array_equal(got[key][e:e + 1], alone[key]), (e, key)
+
+
 # ---- 4. the per-environment pipeline ----------------------------------------------------------------------------------------------------
 def test_per_environment_design_stays_on_the_device():
     """set_env_params (a different body_mass per environment) -> linearize_rollout(T = 1) at the upright state -> solve_dare on the

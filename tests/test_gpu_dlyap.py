@@ -116,10 +116,10 @@ def test_humanoid_policy_evaluation_is_the_dare_solution(ctx):
 
 # ---- 3. the Gramian form, the optional arguments, the sign ----------------------------------------------------------------------------
 def test_gramian_form_and_optional_arguments(ctx):
-    """transpose on (12, 4) and (17, 5) against the restatement; M = A alone; R absent; feedback_sign=+1 with -K bitwise -1 with K;
-    no x0: J is None."""
+    """transpose on (12, 4), (17, 5) and at the edge sizes (16, 9) (the largest one-wave state) and (3, 9) (nu > nx) against the
+    restatement; M = A alone; R absent; feedback_sign=+1 with -K bitwise -1 with K; no x0: J is None."""
     torch, _, data = ctx
-    for nx, nu in ((12, 4), (17, 5)):
+    for nx, nu in ((12, 4), (17, 5), (16, 9), (3, 9)):
         case = lc.gain_case(f"gen{nx}x{nu}", lambda n: dc.generator_case(nx, nu, n), NB)
         lc.judge(case, _solve(torch, data, case, transpose=True), f"dlyap/gramian/gen{nx}x{nu}", record=_record, transpose=True)
     case = lc.gain_case("gen17x5", lambda n: dc.generator_case(17, 5, n), NB)
@@ -137,6 +137,18 @@ def test_gramian_form_and_optional_arguments(ctx):
 def test_failures_are_reported_not_propagated(ctx):
     torch, _, data = ctx
     lc.check_statuses(lambda case, max_iter: _solve(torch, data, case, max_iter=max_iter), "gpu")
+
+
+def test_results_do_not_depend_on_the_batch_position(ctx):
+    """(16, 9), the largest one-wave state: five systems in one launch against each system launched alone, every output bit for bit."""
+    torch, _, data = ctx
+    case = lc.gain_case("gen16x9", lambda n: dc.generator_case(16, 9, n), NB)
+    got = _solve(torch, data, case)
+    assert got["status"].tolist() == [0] * NB and np.isfinite(got["P"]).all()
+    for e in range(NB):
+        alone = _solve(torch, data, {k: v[e:e + 1] for k, v in case.items()})
+        for key in ("P", "J", "change", "iters", "status"):
+            assert np.array_equal(got[key][e:e + 1], alone[key]), (e, key)
 
 
 # ---- 5. properties whose bounds are derived -------------------------------------------------------------------------------------------

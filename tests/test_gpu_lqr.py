@@ -45,7 +45,14 @@ def _compare(tag, got, truth, f64, floor=lc.FLOOR):
 
 
 # ---- 1. the fragment maps of the f64 MFMA ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M,N,K", [(54, 21, 54), (7, 3, 7), (64, 32, 64), (16, 64, 5), (3, 17, 1)])
+# Both variants of the probe at their edges: M = 1 / 15 / 16 with one wave (N <= 64 stays within its four tiles), 17 / 33 / 48 / 49 /
+# 64 with four; N and K below, at and above a tile (16) and a k-step (4).
+PROBE_FIRST = [(54, 21, 54), (7, 3, 7), (64, 32, 64), (16, 64, 5), (3, 17, 1)]
+PROBE_ALL = PROBE_FIRST + [s for s in ((M, N, K) for M in (1, 15, 16, 17, 33, 48, 49, 64) for N in (1, 16, 17, 33, 64) for K in (1, 3, 4, 5, 64))
+                           if s not in PROBE_FIRST]
+
+
+@pytest.mark.parametrize("M,N,K", PROBE_ALL)
 def test_mfma_map_on_exact_integers(ctx, M, N, K):
     """(M x K)(K x N) of small integers through the kernels' tile product equals numpy's bit for bit; asymmetric operands."""
     torch, _, data = ctx
@@ -56,12 +63,25 @@ def test_mfma_map_on_exact_integers(ctx, M, N, K):
     assert np.array_equal(c, a.T @ b)
 
 
+def test_probe_refuses_what_its_tile_slots_do_not_hold(ctx):
+    """One wave holds four tiles and four waves sixteen; no tile beyond them is computed, so the entry point must refuse M or N above
+    64 (tests/test_lqr_host.py enumerates that every shape up to there fits)."""
+    from mujoco_template_amd.exceptions import ConfigError, TemplateError
+
+    torch, _, data = ctx
+    z = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")
+    for a, b in ((z(4, 65), z(4, 1)), (z(4, 1), z(4, 65)), (z(4, 16), z(4, 80))):
+        with pytest.raises((ConfigError, TemplateError), match="must lie in"):
+            data.sim.lqr_gemm_tn(a, b)
+
+
 # ---- 2. the recursion against the restatement -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", ["dense_TB", "permuted_BT"])
-@pytest.mark.parametrize("nx,nu,T", lc.SIZES)
+@pytest.mark.parametrize("nx,nu,T", lc.SIZES + lc.EDGE_BACKWARD)
 def test_recursion_matches_the_restatement(ctx, nx, nu, T, layout):
     """B = 5 distinct systems per launch; from dense [T, B, ...] arrays, and from the permuted [B, T, ...] views of them (what
-    linearize_rollout returns) with Q, R broadcast (one system's cost for all: both strides 0)."""
+    linearize_rollout returns) with Q, R broadcast (one system's cost for all: both strides 0).  With ``lqr_common.EDGE_BACKWARD``
+    every launch variant runs: k_lqr_backward<1, 8>, <1, 32> (nx <= 16 with nu > 8) and <4, 32>, and the horizons T = 1 and 2."""
     import mujoco_template_amd as mt
 
     torch, _, data = ctx
@@ -77,6 +97,7 @@ def test_recursion_matches_the_restatement(ctx, nx, nu, T, layout):
         Q = _dev(torch, p["Q"]).unsqueeze(0).expand(T, B, nx, nx)
         R = _dev(torch, p["R"]).unsqueeze(0).expand(T, B, nu, nu)
         res = mt.lqr_backward(data, A, Bm, lx=lx, lu=lu, lxx=Q, luu=R, VxT=_dev(torch, p["VxT"]), VxxT=_dev(torch, p["VxxT"]), mu=p["mu"], time_major=True)
+        assert res.K.shape == (T, B, nu, nx) and res.k.shape == (T, B, nu)
         got = _np(res)
         got["k"], got["K"] = got["k"].transpose(1, 0, 2), got["K"].transpose(1, 0, 2, 3)
     else:
@@ -85,8 +106,33 @@ def test_recursion_matches_the_restatement(ctx, nx, nu, T, layout):
                               mu=torch.full((B,), p["mu"], dtype=torch.float64, device="cuda"))
         assert res.K.shape == (B, T, nu, nx) and res.k.shape == (B, T, nu)
         got = _np(res)
-    assert (got["status"] == 0).all()
+    assert got["status"].tolist() == [0] * B and got["V0xx"].shape == (B, nx, nx) and got["dV"].shape == (B, 2)
     _compare(f"{layout}/{nx}x{nu}x{T}", got, truth, f64)
+
+
+@pytest.mark.parametrize("nx,nu", [(12, 4), (16, 9), (17, 9)])
+def test_results_do_not_depend_on_the_batch_position(ctx, nx, nu):
+    """One size per launch variant (<1, 8>, <1, 32>, <4, 32>): five systems in one launch against each system launched alone, every
+    output bit for bit."""
+    import mujoco_template_amd as mt
+
+    torch, _, data = ctx
+    T, B = 20, 5
+    p = lc.generate(nx, nu, T, B)
+
+    def run(keep):
+        args = {k: _dev(torch, p[k][:, keep]).permute(1, 0, *range(2, p[k].ndim)) for k in ("A", "B", "lx", "lu")}
+        n = len(keep)
+        return _np(mt.lqr_backward(data, args["A"], args["B"], lx=args["lx"], lu=args["lu"], lxx=_dev(torch, p["Q"][keep]).unsqueeze(1).expand(n, T, nx, nx),
+                                   luu=_dev(torch, p["R"][keep]).unsqueeze(1).expand(n, T, nu, nu), VxT=_dev(torch, p["VxT"][keep]),
+                                   VxxT=_dev(torch, p["VxxT"][keep]), mu=p["mu"]))
+
+    got = run(list(range(B)))
+    assert got["status"].tolist() == [0] * B and np.isfinite(got["K"]).all() and np.abs(got["K"]).max() > 0
+    for e in range(B):
+        alone = run([e])
+        for key in lc.OUTPUTS + ("status",):
+            assert np.array_equal(got[key][e:e + 1], alone[key]), (e, key)
 
 
 # ---- 3. the reference's DARE ----------------------------------------------------------------------------------------------------------------
@@ -212,6 +258,56 @@ def test_candidates(ctx):
         measured(f"lqr/candidates/env{e}", mine, lc.bound(loop), f"(torch float64 loop: {loop:.3e})")
     assert torch.equal(got[:, 0], ud.clamp(lo, hi))
     assert torch.equal(got32, got.to(torch.float32))
+
+
+def _candidates(torch, data, c, alphas, dx0, lo, hi, time_major=False, **kw):
+    """``mt.lqr_candidates`` on a ``lqr_common.candidate_case``: the permuted [B, T, ...] views of its time-major arrays, or with
+    ``time_major`` those arrays themselves.  lo / hi: None, a number or an array [nu]."""
+    import mujoco_template_amd as mt
+
+    perm = lambda x: x if time_major else x.permute(1, 0, *range(2, x.ndim))
+    A, Bm, k, K, u = (perm(_dev(torch, c[key])) for key in ("A", "B", "k", "K", "u"))
+    dev = lambda x: x if x is None or np.ndim(x) == 0 else _dev(torch, x)
+    return mt.lqr_candidates(data, A, Bm, k, K, u, _dev(torch, alphas), dx0=None if dx0 is None else _dev(torch, dx0), lo=dev(lo), hi=dev(hi),
+                             time_major=time_major, **kw)
+
+
+@pytest.mark.parametrize("dx0_kind,bounds_kind", lc.CAND_VARIANTS)
+@pytest.mark.parametrize("nx,nu,T,B,na", lc.CAND_SIZES)
+def test_candidates_at_the_edge_sizes(ctx, nx, nu, T, B, na, dx0_kind, bounds_kind):
+    """``lqr_common.CAND_SIZES`` x ``CAND_VARIANTS`` against the long-double restatement within 8 x the float64 restatement's own error
+    (``lqr_common.judge_candidates``, which also asserts on the restatement that the variant clamps what it says).  A dx0, per
+    trajectory or shared, changes the kernel's result; bounds that are all one number give the same bits passed as that number and
+    as an array; ``time_major=True`` on the [T, B, ...] arrays is bitwise the call on their permuted views; the float32 output is the
+    float64 one rounded once."""
+    torch, _, data = ctx
+    c = lc.candidate_case(nx, nu, T, B, na)
+    dx0, lo, hi = lc.candidate_variant(c, dx0_kind, bounds_kind)
+    res = _candidates(torch, data, c, c["alphas"], dx0, lo, hi)
+    assert res.shape == (B, na, T, nu) and res.dtype == torch.float64
+    lc.judge_candidates(c, res.cpu().numpy(), dx0_kind, bounds_kind, f"lqr/candidates/{nx}x{nu}x{T}x{B}x{na}/{dx0_kind}/{bounds_kind}", record=measured)
+    if dx0 is not None:
+        assert not torch.equal(res, _candidates(torch, data, c, c["alphas"], None, lo, hi))
+    if bounds_kind != "per_actuator":
+        number = lambda x: None if x is None else float(x[0])
+        assert torch.equal(res, _candidates(torch, data, c, c["alphas"], dx0, number(lo), number(hi)))
+    assert torch.equal(res, _candidates(torch, data, c, c["alphas"], dx0, lo, hi, time_major=True))
+    res32 = _candidates(torch, data, c, c["alphas"], dx0, lo, hi, dtype=torch.float32)
+    assert res32.dtype == torch.float32 and torch.equal(res32, res.to(torch.float32))
+
+
+@pytest.mark.parametrize("nx,nu,T,B,na", lc.CAND_SIZES)
+def test_candidates_zero_step_returns_the_clamped_nominal(ctx, nx, nu, T, B, na):
+    """alpha = 0 with dx0 = 0 (absent, and given as zeros) and a nominal inside its bounds, some entries on them: clamp(u) = u bit for
+    bit - dx stays 0."""
+    torch, _, data = ctx
+    c = lc.candidate_case(nx, nu, T, B, na)
+    alphas = np.array([0.0]) if na == 1 else c["alphas"]
+    want = _dev(torch, c["u"]).permute(1, 0, 2).clamp(lc.CAND_LO, lc.CAND_HI)
+    assert alphas[0] == 0.0 and bool((want == lc.CAND_LO).any()) and bool((want == lc.CAND_HI).any())
+    for dx0 in (None, np.zeros((B, nx)), np.zeros(nx)):
+        got = _candidates(torch, data, c, alphas, dx0, lc.CAND_LO, lc.CAND_HI)
+        assert torch.equal(got[:, 0], want)
 
 
 # ---- 7. stream order, no host round trip ------------------------------------------------------------------------------------------------------

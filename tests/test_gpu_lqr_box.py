@@ -15,7 +15,10 @@ from tests.conftest import MODELS, measured
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [(4, 1, 200), (7, 3, 64), (12, 4, 200), (16, 12, 40), (54, 21, 30), (64, 32, 12)]
+# the last three: nu > nx in k_lqr_backward_box<1, 32>, that variant with every tile slot of its wave used, and the smallest system
+# (<1, 8>).  Their long-double references keep every active-set decision at least 5e-6 from its threshold (MARGIN_MIN is 1e-6) with
+# the seeds and horizons as they stand: nothing had to be changed for the module's rule.
+SIZES = [(4, 1, 200), (7, 3, 64), (12, 4, 200), (16, 12, 40), (54, 21, 30), (64, 32, 12), (3, 9, 40), (16, 32, 12), (1, 1, 20)]
 B = 3
 
 

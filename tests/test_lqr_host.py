@@ -77,8 +77,34 @@ def host_backward(lib, p, luu=None, mu=None):
     return out
 
 
+def host_candidates(lib, c, alphas, dx0, lo, hi, f32=False):
+    """The emulated candidate kernel on a ``lqr_common.candidate_case`` (dense time-major inputs); dx0 None, [B, nx] or a shared [nx];
+    lo / hi None or [nu].  The output starts as NaN so that anything not written shows."""
+    T, B, nx, nu = c["A"].shape[0], c["A"].shape[1], c["A"].shape[2], c["B"].shape[3]
+    alphas, dx0, lo, hi = (None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (alphas, dx0, lo, hi))
+    cand = np.full((B, len(alphas), T, nu), np.nan, dtype=np.float32 if f32 else np.float64)
+    a = CandArgs(T=T, B=B, nx=nx, nu=nu, nalpha=len(alphas), out_f32=int(f32))
+    a.A, a.Bm = Strided(c["A"].ctypes.data, B * nx * nx, nx * nx), Strided(c["B"].ctypes.data, B * nx * nu, nx * nu)
+    a.k, a.K, a.u = Strided(c["k"].ctypes.data, B * nu, nu), Strided(c["K"].ctypes.data, B * nu * nx, nu * nx), Strided(c["u"].ctypes.data, B * nu, nu)
+    a.dx0 = Strided(None, 0, 0) if dx0 is None else Strided(dx0.ctypes.data, 0, nx if dx0.ndim == 2 else 0)
+    a.alphas, a.cand = alphas.ctypes.data, cand.ctypes.data
+    a.lo, a.hi = (None if x is None else x.ctypes.data for x in (lo, hi))
+    assert lib.lqrh_candidates(ctypes.byref(a)) == 0
+    return cand
+
+
 # ---- 1. the kernel source on host threads ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M,N,K", [(54, 21, 54), (7, 3, 7), (64, 32, 64), (16, 64, 5), (3, 17, 1)])
+# Both variants of the probe at their edges, M = 1 / 15 / 16 with one wave (N <= 64 stays within its four tiles) and 17 / 33 / 48 /
+# 49 / 64 with four, N and K below, at and above a tile and a k-step.  The GPU suite runs the full product (200 shapes); a block of
+# host threads costs more than a launch, so here: every (M, N) at K = 5 (a full k-step and a partial one), and every K at the four
+# corner shapes of each variant.
+PROBE_FIRST = [(54, 21, 54), (7, 3, 7), (64, 32, 64), (16, 64, 5), (3, 17, 1)]
+PROBE_M1, PROBE_M4, PROBE_N, PROBE_K = (1, 15, 16), (17, 33, 48, 49, 64), (1, 16, 17, 33, 64), (1, 3, 4, 5, 64)
+PROBE_ALL = PROBE_FIRST + [s for s in ((M, N, K) for M in PROBE_M1 + PROBE_M4 for N in PROBE_N for K in PROBE_K) if s not in PROBE_FIRST]
+PROBE_HOST = [(M, N, K) for M, N, K in PROBE_ALL if (M, N, K) in PROBE_FIRST or K == 5 or (M in (1, 16, 17, 64) and N in (1, 64))]
+
+
+@pytest.mark.parametrize("M,N,K", PROBE_HOST)
 def test_tile_product_on_exact_integers(driver, M, N, K):
     """Small integers: every partial sum is exact, so the result must equal numpy's bit for bit whatever the summation order - any
     slip in the fragment maps (operand lane -> (row, k), result register -> row) or in the edge masking shows as a wrong entry.  The
@@ -91,14 +117,16 @@ def test_tile_product_on_exact_integers(driver, M, N, K):
     assert np.array_equal(c, a.T @ b)
 
 
-@pytest.mark.parametrize("nx,nu,T", [(4, 1, 200), (7, 3, 64), (12, 4, 200), (54, 21, 20)])
+@pytest.mark.parametrize("nx,nu,T", [(4, 1, 200), (7, 3, 64), (12, 4, 200), (54, 21, 20)] + lc.EDGE_BACKWARD)
 def test_recursion_matches_the_restatement(driver, nx, nu, T):
-    """Error of each output against the long-double restatement, bounded by 8 x the float64 restatement's own error (floor 1e-13)."""
+    """Error of each output against the long-double restatement, bounded by 8 x the float64 restatement's own error (floor 1e-13).
+    With ``lqr_common.EDGE_BACKWARD`` every launch variant runs: <1, 8>, <1, 32> (nx <= 16 with nu > 8) and <4, 32>, and T = 1, 2."""
     B = 2 if nx > 16 else 3
     p = lc.generate(nx, nu, T, B)
     truth, f64 = lc.restate_batch(p, np.longdouble), lc.restate_batch(p, np.float64)
     got = host_backward(driver, p)
     assert (truth["status"] == 0).all() and (got["status"] == 0).all()
+    assert got["K"].shape == (B, T, nu, nx) and got["k"].shape == (B, T, nu) and got["status"].tolist() == [0] * B
     for key in lc.OUTPUTS:
         mine, numpy64 = lc.rel_err(got[key], truth[key]), lc.rel_err(f64[key], truth[key])
         print(f"{(nx, nu, T)} {key}: kernel {mine:.2e}  float64 numpy {numpy64:.2e}")
@@ -178,6 +206,50 @@ def test_candidates_match_the_restatement(driver):
     assert np.array_equal(got32, got.astype(np.float32))                              # rounded once
 
 
+@pytest.mark.parametrize("nx,nu", [(12, 4), (16, 9), (17, 9)])
+def test_results_do_not_depend_on_the_batch_position(driver, nx, nu):
+    """One size per launch variant (<1, 8>, <1, 32>, <4, 32>): five systems in one launch against each system launched alone, every
+    output bit for bit.  The emulation runs the systems one after the other in the SAME LDS buffer, so a read of LDS that the
+    system itself has not written would show here."""
+    T, B = 6, 5
+    p = lc.generate(nx, nu, T, B)
+    got = host_backward(driver, p)
+    assert got["status"].tolist() == [0] * B
+    for e in range(B):
+        sub = {k: (v[:, e:e + 1] if k in ("A", "B", "lx", "lu") else v[e:e + 1] if isinstance(v, np.ndarray) else v) for k, v in p.items()}
+        alone = host_backward(driver, sub)
+        for key in lc.OUTPUTS + ("status",):
+            assert np.array_equal(got[key][e:e + 1], alone[key]), (e, key)
+
+
+@pytest.mark.parametrize("dx0_kind,bounds_kind", lc.CAND_VARIANTS)
+@pytest.mark.parametrize("nx,nu,T,B,na", lc.CAND_HOST_SIZES)
+def test_candidates_at_the_edge_sizes(driver, nx, nu, T, B, na, dx0_kind, bounds_kind):
+    """``lqr_common.CAND_HOST_SIZES`` x ``CAND_VARIANTS`` against the long-double restatement (``lqr_common.judge_candidates``); a dx0
+    changes the kernel's result as it changes the restatement's; the float32 output is the float64 one rounded once."""
+    c = lc.candidate_case(nx, nu, T, B, na)
+    dx0, lo, hi = lc.candidate_variant(c, dx0_kind, bounds_kind)
+    got = host_candidates(driver, c, c["alphas"], dx0, lo, hi)
+    lc.judge_candidates(c, got, dx0_kind, bounds_kind, f"lqr/host/candidates/{nx}x{nu}x{T}x{B}x{na}/{dx0_kind}/{bounds_kind}")
+    if dx0 is not None:
+        assert not np.array_equal(got, host_candidates(driver, c, c["alphas"], None, lo, hi))
+    assert np.array_equal(host_candidates(driver, c, c["alphas"], dx0, lo, hi, f32=True), got.astype(np.float32))
+
+
+@pytest.mark.parametrize("nx,nu,T,B,na", lc.CAND_HOST_SIZES)
+def test_candidates_zero_step_returns_the_clamped_nominal(driver, nx, nu, T, B, na):
+    """alpha = 0 with dx0 = 0 (absent, and given as zeros) and a nominal inside its bounds, some entries on them: clamp(u) = u bit for
+    bit - dx stays 0."""
+    c = lc.candidate_case(nx, nu, T, B, na)
+    lo, hi = np.full(nu, lc.CAND_LO), np.full(nu, lc.CAND_HI)
+    alphas = np.array([0.0]) if na == 1 else c["alphas"]
+    want = np.clip(c["u"], lo, hi).transpose(1, 0, 2)
+    assert (want == lo).any() and (want == hi).any()
+    for dx0 in (None, np.zeros((B, nx)), np.zeros(nx)):
+        got = host_candidates(driver, c, alphas, dx0, lo, hi)
+        assert alphas[0] == 0.0 and np.array_equal(got[:, 0], want)
+
+
 # ---- 2. host arithmetic -----------------------------------------------------------------------------------------------------------------
 def test_highest_element_matches_enumeration(driver):
     def hi(*a):
@@ -201,12 +273,37 @@ def test_size_limits_and_lds_layouts(driver):
     ok = driver.lqrh_size_error
     assert ok(1, 1, 64, 32) == 0 and ok(100, 4096, 4, 1) == 0
     assert ok(0, 1, 4, 1) == 1 and ok(1, 0, 4, 1) == 2 and ok(1, 1, 65, 1) == 3 and ok(1, 1, 0, 1) == 3 and ok(1, 1, 4, 33) == 4 and ok(1, 1, 4, 0) == 4
-    for nx in (1, 2, 4, 7, 16, 17, 54, 64):
-        for nu in (1, 3, 8, 9, 21, 32):
-            assert driver.lqrh_layout_ok(nx, nu) == 1, (nx, nu)
-            assert driver.lqrh_lds_bytes(nx, nu) <= 160 * 1024, (nx, nu)
-            assert driver.lqrh_cand_lds_bytes(nx, nu, 64) <= 160 * 1024, (nx, nu)
+    sizes = [(nx, nu) for nx in (1, 2, 4, 7, 16, 17, 54, 64) for nu in (1, 3, 8, 9, 21, 32)]
+    for nx, nu in sizes + [s for s in lc.EDGE_SIZES if s not in sizes]:
+        assert ok(1, 1, nx, nu) == 0, (nx, nu)
+        assert driver.lqrh_layout_ok(nx, nu) == 1, (nx, nu)
+        assert driver.lqrh_lds_bytes(nx, nu) <= 160 * 1024, (nx, nu)
+        assert driver.lqrh_cand_lds_bytes(nx, nu, 64) <= 160 * 1024, (nx, nu)
     assert driver.lqrh_lds_bytes(4, 1) < 2048                   # the cart-pole: many workgroups per compute unit
+
+
+def test_no_accepted_shape_has_more_tiles_than_the_waves_hold(driver):
+    """``lqr_gemm_tn`` / ``dare_gemm`` give each of the NW waves at most four 16 x 16 tiles and compute no tile beyond 4 NW, so every
+    product of every accepted shape must fit: the products of the backward passes, of DARE and of the Lyapunov kernel are
+    (nx or nu) x (nx or nu) with NW = lqr_waves(nx), the probe's is M x N with one wave for M <= 16 and four above (M, N <= 64 is what
+    ``mjb_lqr_gemm_tn`` accepts).  The shapes that fill every slot - (16, 32) and (64, 32), the probe's (16, 64) and (64, 64) - are
+    among those the exact-integer and restatement tests run."""
+    tiles = lambda M, N: ((M + 15) // 16) * ((N + 15) // 16)
+    full = set()
+    for nx in range(1, 65):
+        nw = driver.lqrh_waves(nx)
+        assert nw == (1 if nx <= 16 else 4)
+        for nu in range(1, 33):
+            assert driver.lqrh_size_error(1, 1, nx, nu) == 0
+            most = max(tiles(M, N) for M in (nx, nu) for N in (nx, nu))
+            assert most <= 4 * nw, (nx, nu, most)
+            if most == 4 * nw:
+                full.add((nx, nu))
+    assert (16, 32) in full and (64, 32) in full and (15, 16) not in full
+    for M in range(1, 65):
+        for N in range(1, 65):
+            assert tiles(M, N) <= 4 * (1 if M <= 16 else 4), (M, N)
+    assert driver.lqrh_size_error(1, 1, 65, 1) == 3 and driver.lqrh_size_error(1, 1, 4, 33) == 4      # beyond them the entry points refuse
 
 
 # ---- 3. cross-compilation ---------------------------------------------------------------------------------------------------------------
