@@ -609,6 +609,59 @@ typedef struct mjbSetpoint {
 } mjbSetpoint;
 int mjb_setpoint_ctrl(mjbData* d, const mjbSetpoint* p);
 
+/* ---- the linear feedback law from device tensors: per-environment and time-varying gains.  It is the law of the reference's LQR
+ * controllers (examples/humanoid/controllers/lqr.py:147-170, examples/drone/controllers/lqr.py:220-278: mj_differentiatePos against the
+ * goal, ctrl0 - K dx, clip to ctrlrange) with K, u0, q0, v0 read where mjb_setpoint_ctrl, mjb_lqr_dare and mjb_lqr_backward left them:
+ * device memory, one block per environment and / or per step.  mjb_set_feedback / MJB_CTRL_FEEDBACK / mjb_feedback_ctrl keep their one
+ * host-supplied law shared by all environments and are not involved.
+ * For environment e of the data object at step index t, all arithmetic in float64, float32 inputs widened exactly:
+ *   dx  = [ differentiatePos(q0 -> qpos_e, dt = 1) ; qvel_e - v0 ]      # 2nv
+ *   s_a = sum_k K[a, k] dx[k]
+ *   u_a = u0[a] + feedback_sign * s_a
+ *   if clip and actuator a is ctrl-limited: u_a = min(max(u_a, lo_a), hi_a)
+ *   ctrl_e[a] = u_a                                                     # rounded once to the data's dtype
+ * The sign and quaternion rule of dx are those of mjb_differentiate_pos(qvel_out, 1, q0, qpos).  Every product K[a, k] dx[k] is rounded
+ * once and row a is added in the order k = 0 .. 2nv - 1.
+ * Inputs: K [nu, 2nv] row-major, u0 [nu], q0 [nq], v0 [nv] (v0.ptr NULL = zeros), each an mjbStridedIn: the block of (t, e) sits at
+ * ptr + t * step_stride + e * env_stride (strides in elements, >= 0, 0 = broadcast), MJB_F32 or MJB_F64 per array.  Strides (0, 0): a
+ * shared law; (0, n): per environment (domain-randomised LQR); (n, 0): time-varying (TVLQR tracking); both: per environment and step
+ * (the closed-loop forward pass of iLQR with u0 = ubar + alpha k, q0 / v0 the nominal state, feedback_sign = +1).  qpos, qvel and ctrl
+ * are the data object's own arrays; nq, nv, nu, the joint table and actuator_ctrllimited / actuator_ctrlrange its model's.
+ * nv <= 64, 1 <= nu <= 32 (the limits of mjb_lqr_dare).
+ * feedback_sign: -1 is the convention of mjb_lqr_dare and mjb_set_feedback (u = u0 - K dx), +1 that of mjb_lqr_backward; anything else
+ * is MJB_ERR_ARG.  clip = 0 leaves u_a unclipped.
+ * env_mask: optional [batch] bytes in device memory; a zero entry = that environment's ctrl, status and record row are not written
+ * (the bytes of mjb_lqr_dare's status == 0 feed it directly).
+ * status: optional [batch] int32 in device memory; bits are ORed in, so it is sticky over the steps of a rollout (the caller zeroes it).
+ *   bit 0 (1): a value of this environment's K, u0, q0, v0, qpos or qvel, or a resulting u_a, was not finite.  That step's ctrl is then
+ *              written as ZEROS for the whole environment (what MuJoCo does with a bad ctrl): a failed design cannot be applied silently.
+ *   bit 1 (2): at least one actuator was clipped (not reported for a step that raised bit 0).
+ * u_rec: optional record in the data's dtype; the ctrl row just written is also stored at u_rec + t * u_rec_step_stride +
+ *   e * u_rec_env_stride - the control tensor of the closed-loop trajectory, [batch, T, nu] as mjb_rollout_ctrl and mjb_lqr_backward take it.
+ * One wavefront owns an environment: status is a plain load, OR and store, without atomics, and an environment's ctrl is bitwise the
+ * same at any position of any batch, for any batch size, alignment of its K block and layout of the inputs.
+ *
+ * mjb_feedback_law: ONE launch on the data's stream; writes ctrl for step index t.  No scratch memory, no allocation, no host copy, no
+ * synchronisation.
+ * mjb_rollout_feedback: for t = 0 .. nstep-1 it enqueues, in order, (1) the law kernel for t, (2) exactly what mjb_step(d, 1) enqueues,
+ * (3) when spec != NULL and (t + 1) % obs_every == 0, what mjb_obs_gather enqueues, into row t / obs_every of obs_out_dev
+ * [nstep / obs_every, batch, dim]: a ring row holds what the ring of mjb_rollout_ctrl holds for the same controls.  Everything is
+ * stream-ordered; no synchronisation and no host read between steps.
+ * Checked before anything is launched (MJB_ERR_ARG with a message; state, ctrl and engine flags untouched): the sizes, feedback_sign,
+ * nstep >= 1, t >= 0, strides >= 0, the required pointers (K, u0, q0), every pointer device memory of the data's device
+ * (hipPointerGetAttributes), and the highest element read or written inside the allocation behind it (hipMemGetAddressRange) - for
+ * the rollout with t = nstep-1; u_rec, status, env_mask and the ring included. */
+typedef struct mjbFeedbackLaw {
+  mjbStridedIn K, u0, q0, v0;
+  int feedback_sign, clip;
+  const unsigned char* env_mask;
+  int* status;
+  void* u_rec; long u_rec_step_stride, u_rec_env_stride;
+} mjbFeedbackLaw;
+int mjb_feedback_law(mjbData* d, const mjbFeedbackLaw* p, int t);
+int mjb_rollout_feedback(mjbData* d, const mjbFeedbackLaw* p, int nstep,
+                         const mjbObsSpec* spec, void* obs_out_dev, int obs_every);
+
 /* ---- mj_jacSite / mj_jacBody / mj_jacBodyCom / mj_jacSubtreeCom (reference jacobians.py:44-79).
  * kinds[i]: 0 site, 1 body, 2 bodycom, 3 subtreecom.  jacp/jacr host [batch, nreq, 3, nv] float64 (jacr may be NULL) ---- */
 int mjb_jac(mjbData* d, int nreq, const int* kinds, const int* ids, double* jacp_host, double* jacr_host);

@@ -18,6 +18,7 @@ from .controllers import LinearFeedbackController, PositionTargetDemo, RandomCtr
 from .device_data import DeviceData
 from .env import Env, StepResult
 from .exceptions import CompatibilityError, ConfigError, LinearizationError, NameLookupError, TemplateError
+from .feedback import DeviceFeedbackController, FeedbackRollout, feedback_ctrl, rollout_feedback
 from .jacobians import compute_requested_jacobians
 from .linearization import linearize_discrete
 from .model import ModelHandle
@@ -38,5 +39,6 @@ __all__ = [
     "compute_requested_jacobians", "StepHook", "iterate_passive", "run_passive_headless", "steady_ctrl0", "DataProbe",
     "StateControlRecorder", "TrajectoryLogger", "rollout", "linearize_rollout", "ObservationDict", "DeviceData", "uses_device_arrays",
     "ObservationArray", "Observation", "JacobianDict", "JacobiansDict", "InfoDict", "StateSnapshot", "lqr_backward", "lqr_candidates", "trajectory_cost", "select_candidates", "TrajCostResult", "TrajSelectResult",
-    "LqrBackwardResult", "LqrBoxResult", "solve_dare", "DareResult", "closed_loop_poles", "PolesResult", "closed_loop_cost", "LyapResult", "solve_setpoint", "steady_ctrl0_device", "SetpointResult", "__version__",
+    "LqrBackwardResult", "LqrBoxResult", "solve_dare", "DareResult", "closed_loop_poles", "PolesResult", "closed_loop_cost", "LyapResult", "solve_setpoint", "steady_ctrl0_device", "SetpointResult",
+    "feedback_ctrl", "rollout_feedback", "FeedbackRollout", "DeviceFeedbackController", "__version__",
 ]

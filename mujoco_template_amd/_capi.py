@@ -102,6 +102,13 @@ class SetpointStruct(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("ctrl", "sv", "rcond", "residual", "pinv", "rank", "sweeps", "status")]
 
 
+class FeedbackLawStruct(ctypes.Structure):
+    """``mjbFeedbackLaw`` (include/mjbatch.h)."""
+    _fields_ = [(n, StridedIn) for n in ("K", "u0", "q0", "v0")] + [(n, ctypes.c_int) for n in ("feedback_sign", "clip")] + \
+               [(n, ctypes.c_void_p) for n in ("env_mask", "status", "u_rec")] + \
+               [(n, ctypes.c_long) for n in ("u_rec_step_stride", "u_rec_env_stride")]
+
+
 class TrajSelectStruct(ctypes.Structure):
     """``mjbTrajSelect`` (include/mjbatch.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("nprob", "ncand", "T", "nu", "mode", "cand_dtype", "out_dtype")] + \
@@ -198,6 +205,8 @@ def load_library() -> ctypes.CDLL:
     L.mjb_traj_cost.restype = ci
     L.mjb_traj_select.argtypes = [vp, ctypes.POINTER(TrajSelectStruct)]
     L.mjb_traj_select.restype = ci
+    L.mjb_feedback_law.argtypes = [vp, ctypes.POINTER(FeedbackLawStruct), ci]
+    L.mjb_rollout_feedback.argtypes = [vp, ctypes.POINTER(FeedbackLawStruct), ci, vp, vp, ci]
     L.mjb_jac.argtypes = [vp, ci, vp, vp, vp, vp]
     L.mjb_profile_get.argtypes = [vp, vp]
     L.mjb_profile_get.restype = ci
@@ -234,7 +243,7 @@ def load_library() -> ctypes.CDLL:
                  "mjb_model_load", "mjb_model_load_xml", "mjb_model_load_xml_string", "mjb_integrate_pos", "mjb_differentiate_pos", "mjb_host_view", "mjb_sync_to_host", "mjb_sync_to_device",
                  "mjb_step_host", "mjb_mirror_edited_mask", "mjb_mirror_commit", "mjb_step_host_auto", "mjb_engine_flags",
                  "mjb_reset_envs", "mjb_forward_envs", "mjb_engine_flags_peek", "mjb_set_env_param", "mjb_get_env_param", "mjb_clear_env_param",
-                 "mjb_env_param_mask"):
+                 "mjb_env_param_mask", "mjb_feedback_law", "mjb_rollout_feedback"):
         getattr(L, name).restype = ci
     _LIB = L
     return L
@@ -1129,6 +1138,36 @@ class BatchSim:
         struct = TrajSelectStruct()
         struct.temperature = float(sizes.get("temperature", 0.0))
         self._lqr_call(load_library().mjb_traj_select, struct, {k: v for k, v in sizes.items() if k != "temperature"}, {}, pointers, keep)
+
+    def _feedback_struct(self, arrays: dict, options: dict) -> "FeedbackLawStruct":
+        struct = FeedbackLawStruct()
+        for k, v in arrays.items():                                 # (address, step stride, env stride, dtype code: 0 float32, 1 float64)
+            setattr(struct, k, StridedIn(v[0] or None, int(v[1]), int(v[2]), int(v[3])))
+        struct.feedback_sign, struct.clip = int(options["feedback_sign"]), int(bool(options["clip"]))
+        for k in ("env_mask", "status", "u_rec"):
+            setattr(struct, k, options.get(k) or None)
+        struct.u_rec_step_stride, struct.u_rec_env_stride = int(options.get("u_rec_step_stride", 0)), int(options.get("u_rec_env_stride", 0))
+        return struct
+
+    def feedback_law(self, arrays: dict, options: dict, t: int = 0, keep=()) -> None:
+        """``mjb_feedback_law`` on raw device addresses: ``arrays`` K, u0, q0 and optionally v0 as (address, step stride, env stride, dtype
+        code: 0 float32, 1 float64); ``options`` feedback_sign, clip and the addresses env_mask, status, u_rec (0 = absent) with
+        u_rec_step_stride / u_rec_env_stride.  Writes ``ctrl`` for step index ``t`` on torch's current stream; nothing waits for the GPU.
+        ``feedback.feedback_ctrl`` is the checked tensor interface on top of it."""
+        struct = self._feedback_struct(arrays, options)
+        self.use_torch_stream()
+        self._feedback_keep = keep                                  # alive at least until the next call on this object
+        _check(load_library().mjb_feedback_law(self.ptr, ctypes.byref(struct), int(t)))
+
+    def rollout_feedback(self, arrays: dict, options: dict, nstep: int, obs_spec: ObsSpecHandle | None = None, obs_out_ptr: int = 0,
+                         obs_every: int = 0, keep=()) -> None:
+        """``mjb_rollout_feedback`` on raw device addresses (see ``feedback_law``): per step the law kernel, what ``step(1)`` enqueues and,
+        every ``obs_every`` steps, what ``obs_gather`` enqueues into the ring.  ``feedback.rollout_feedback`` is the tensor interface."""
+        struct = self._feedback_struct(arrays, options)
+        self.use_torch_stream()
+        self._feedback_keep = keep
+        _check(load_library().mjb_rollout_feedback(self.ptr, ctypes.byref(struct), int(nstep), obs_spec.ptr if obs_spec else None,
+                                                   ctypes.c_void_p(obs_out_ptr) if obs_out_ptr else None, int(obs_every)))
 
     def lqr_gemm_tn(self, a, b):
         """``a [K, M]``, ``b [K, N]`` float64 tensors on this GPU -> ``a.T @ b`` through the kernels' f64 MFMA tile product alone."""

@@ -25,6 +25,7 @@
 #include "mjb_dlyap.hpp"
 #include "mjb_setpoint.hpp"
 #include "mjb_traj.hpp"
+#include "mjb_feedback.hpp"
 
 using namespace mjb;
 
@@ -1996,6 +1997,77 @@ int mjb_traj_select(mjbData* d, const mjbTrajSelect* p) {
   a.cost = p->cost; a.cand = p->cand; a.u_out = p->u_out; a.best = p->best; a.best_cost = p->best_cost; a.weights = p->weights;
   const hipError_t e = traj_launch_select(a, d->stream);
   if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_traj_select launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+// ---- mjb_feedback_law / mjb_rollout_feedback: the checks; the kernel and its launch are in mjb_feedback.hip ----
+// Everything both entry points check, for the steps t0 .. t0 + nstep - 1, and the kernel's arguments (t left to the caller).
+static int feedback_args(mjbData* d, const char* fn, const mjbFeedbackLaw* p, int t0, int nstep, FeedbackLawArgs& a) {
+  if (!d || !p) return fail(MJB_ERR_ARG, std::string(fn) + ": NULL argument");
+  const HostModel& h = d->model->h;
+  std::memset(&a, 0, sizeof(a));
+  a.B = d->batch; a.nq = h.nq; a.nv = h.nv; a.nu = h.nu; a.njnt = h.njnt; a.data_f32 = d->dtype == MJB_F32; a.clip = p->clip ? 1 : 0; a.t = t0;
+  a.sign = (double)p->feedback_sign;
+  const mjbStridedIn* src[4] = {&p->K, &p->u0, &p->q0, &p->v0};
+  FbIn* dst[4] = {&a.K, &a.u0, &a.q0, &a.v0};
+  static const char* const names[4] = {"K", "u0", "q0", "v0"};
+  for (int k = 0; k < 4; k++) {
+    if (src[k]->ptr && src[k]->dtype != MJB_F32 && src[k]->dtype != MJB_F64)
+      return fail(MJB_ERR_ARG, std::string(fn) + ": the dtype of " + names[k] + " must be MJB_F32 or MJB_F64");
+    dst[k]->p = src[k]->ptr; dst[k]->ss = src[k]->step_stride; dst[k]->es = src[k]->env_stride; dst[k]->f32 = src[k]->dtype == MJB_F32;
+  }
+  a.ur_ss = p->u_rec_step_stride; a.ur_es = p->u_rec_env_stride;
+  static const char* const msg[10] = {"", ": the data object has no environment", ": nv must lie in [1, 64]", ": nu must lie in [1, 32]",
+                                      ": the model's joint table does not fit nq, nv", ": feedback_sign must be -1 or +1", ": t must be >= 0",
+                                      ": nstep must be >= 1 (and t + nstep <= 2^30)", ": strides must be >= 0", ": K, u0 and q0 are required"};
+  if (const int why = feedback_arg_error(a, nstep)) return fail(MJB_ERR_ARG, std::string(fn) + msg[why]);
+  HIPCHK(hipSetDevice(d->device));
+  const long B = d->batch, last = (long)t0 + nstep - 1, nx = 2L * h.nv;
+  const long n[4] = {(long)h.nu * nx, h.nu, h.nq, h.nv};
+  int rc;
+  for (int k = 0; k < 4; k++)
+    if ((rc = check_traj_array(d, fn, names[k], src[k]->ptr, k == 3, last + 1, B, n[k], src[k]->step_stride, src[k]->env_stride,
+                               src[k]->dtype == MJB_F32 ? 4 : 8)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "u_rec", p->u_rec, true, last + 1, B, h.nu, p->u_rec_step_stride, p->u_rec_env_stride, a.data_f32 ? 4 : 8)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "status", p->status, true, 1, B, 1, 0, 1, 4)) != MJB_OK) return rc;
+  if ((rc = check_traj_array(d, fn, "env_mask", p->env_mask, true, 1, B, 1, 0, 1, 1)) != MJB_OK) return rc;
+  if (a.data_f32) { a.qpos = d->df.qpos; a.qvel = d->df.qvel; a.ctrl = d->df.ctrl; }
+  else { a.qpos = d->dd.qpos; a.qvel = d->dd.qvel; a.ctrl = d->dd.ctrl; }
+  a.jnt_type = d->md.jnt_type; a.jnt_qposadr = d->md.jnt_qposadr; a.jnt_dofadr = d->md.jnt_dofadr;
+  a.ctrllimited = d->md.actuator_ctrllimited; a.ctrlrange = d->md.actuator_ctrlrange;
+  a.mask = p->env_mask; a.status = p->status; a.u_rec = p->u_rec;
+  return MJB_OK;
+}
+
+int mjb_feedback_law(mjbData* d, const mjbFeedbackLaw* p, int t) {
+  FeedbackLawArgs a;
+  int rc = feedback_args(d, "mjb_feedback_law", p, t, 1, a);
+  if (rc != MJB_OK) return rc;
+  const hipError_t e = feedback_launch(a, d->stream);
+  if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_feedback_law launch: ") + hipGetErrorString(e));
+  return MJB_OK;
+}
+
+int mjb_rollout_feedback(mjbData* d, const mjbFeedbackLaw* p, int nstep, const mjbObsSpec* spec, void* obs_out_dev, int obs_every) {
+  static const char* fn = "mjb_rollout_feedback";
+  FeedbackLawArgs a;
+  int rc = feedback_args(d, fn, p, 0, nstep, a);
+  if (rc != MJB_OK) return rc;
+  const bool ring = spec && obs_out_dev && obs_every > 0;
+  const long rows = ring ? nstep / obs_every : 0;
+  const size_t esize = d->dtype == MJB_F32 ? 4 : 8;
+  if (ring && rows > 0 && (rc = check_traj_array(d, fn, "obs_out_dev", obs_out_dev, false, rows, d->batch, spec->dev.dim, (long)d->batch * spec->dev.dim,
+                                                   spec->dev.dim, esize)) != MJB_OK) return rc;
+  if ((rc = engine_check(d)) != MJB_OK) return rc;               // what the first step's launch would refuse, before the first law kernel
+  ObsSpecDev none; std::memset(&none, 0, sizeof(none));
+  for (int t = 0; t < nstep; t++) {
+    a.t = t;
+    const hipError_t e = feedback_launch(a, d->stream);
+    if (e != hipSuccess) return fail(MJB_ERR_DEVICE, std::string("mjb_rollout_feedback launch: ") + hipGetErrorString(e));
+    if ((rc = launch(d, make_args(d, 1, MJB_CTRL_KEEP, 0, 0, 1.0, 0), none, nullptr, false)) != MJB_OK) return rc;   // mjb_step(d, 1)
+    if (ring && (t + 1) % obs_every == 0 &&
+        (rc = mjb_obs_gather(d, spec, (char*)obs_out_dev + (size_t)(t / obs_every) * d->batch * spec->dev.dim * esize)) != MJB_OK) return rc;
+  }
   return MJB_OK;
 }
 

@@ -38,6 +38,19 @@ def _launch(fn: str, model: MjModel, data: MjData, control, initial_state, initi
     launch recording the ring.  Returns ``(buf, nstep, time_col)``: ``buf [nstep (+ 1), B, dim]`` with ring row ``t`` (the state after
     step ``t``: qpos | qvel | sensordata | time [| qacc_warmstart]) at ``buf[t + lead_row]``; with ``lead_row`` the columns qpos, qvel
     and qacc_warmstart of ``buf[0]`` hold the start state, so that ``buf[t]`` is the state BEFORE step ``t`` for every ``t``."""
+    buf, ring, spec, nstep, time_col = _front(fn, model, data, control, initial_state, initial_warmstart, nstep, warmstart, lead_row)
+    sim = data.sim
+    if control is None:
+        sim.rollout(nstep, CTRL_KEEP, obs_spec=spec, obs_out_ptr=ring.data_ptr(), obs_every=1)
+    else:
+        sim.rollout_ctrl(nstep, control, obs_spec=spec, obs_out_ptr=ring.data_ptr(), obs_every=1)
+    data.mark_device_newer()
+    return buf, nstep, time_col
+
+
+def _front(fn: str, model: MjModel, data: MjData, control, initial_state, initial_warmstart, nstep, warmstart: bool, lead_row: bool):
+    """Everything of ``_launch`` before the launch (also the front of ``feedback.rollout_feedback``): the checks, the start state and
+    warm start written through the device arrays, the ring and its obs spec.  Returns ``(buf, ring, spec, nstep, time_col)``."""
     import torch
 
     _check(model, data)
@@ -92,12 +105,7 @@ def _launch(fn: str, model: MjModel, data: MjData, control, initial_state, initi
         buf[0, :, nq:nq + nv].copy_(sim.torch_view("qvel"))
         buf[0, :, time_col + 1:].copy_(ws)
     ring = buf[1:] if lead_row else buf
-    if control is None:
-        sim.rollout(nstep, CTRL_KEEP, obs_spec=spec, obs_out_ptr=ring.data_ptr(), obs_every=1)
-    else:
-        sim.rollout_ctrl(nstep, control, obs_spec=spec, obs_out_ptr=ring.data_ptr(), obs_every=1)
-    data.mark_device_newer()
-    return buf, nstep, time_col
+    return buf, ring, spec, nstep, time_col
 
 
 def _results(ring, time_col: int, nx: int):
