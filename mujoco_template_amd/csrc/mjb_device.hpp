@@ -1314,6 +1314,29 @@ template <typename T> MJB_DEV void quat_rot(T* r, const T* q, const T* v) {
   mulmatvec3(r, R, v);
 }
 
+// The world body's entries of the arrays OUTSIDE the overlay region (make_layout): its pose and inertial frame, its zero inertia and
+// its zero velocity.  Model-independent constants that no phase changes: every per-body loop of kinematics, com_pos and the velocity
+// stage starts at body 1, so do the per-level / per-round fall-backs of kinematics and of the tree sums (lanes own bodies 1 + lane;
+// a round writes the PARENT of a body, and only cfrc / crb / subtree_com are summed upwards); the flat ancestor sum rewrites cvel[0]
+// with itself (no ancestors: + 0); reset_state restores qpos, qvel, qacc, the warm start and ctrl and nothing else.  So the kernels
+// write them once, where they clear M, before their step loop; the caller's next gsync publishes them.  The world body's entries
+// INSIDE the overlay (xmat, cfrc, and cacc unless the model has accelerometers) are overwritten by other phases' temporaries and stay
+// with their phases.
+template <typename T, int G> MJB_DEV void world_body_consts(Ctx<T>& c) {
+  MJB_ENV(c); T* w = c.w;
+  T *xpos = w + L.xpos, *xquat = w + L.xquat, *xipos = w + L.xipos, *ximat = w + L.ximat, *cin = w + L.cinert, *cvel = w + L.cvel;
+  if (c.lane == 0) {
+    xpos[0] = xpos[1] = xpos[2] = 0; xquat[0] = 1; xquat[1] = xquat[2] = xquat[3] = 0;
+    xipos[0] = xipos[1] = xipos[2] = 0;
+#pragma unroll
+    for (int k = 0; k < 9; k++) ximat[k] = (k % 4 == 0) ? (T)1 : (T)0;
+#pragma unroll
+    for (int k = 0; k < 10; k++) cin[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) cvel[k] = 0;
+  }
+}
+
 // Three stages instead of one long per-level body loop (only a few lanes are active per tree level):
 //   (1) all bodies in parallel: pose of the body RELATIVE TO ITS PARENT (joint chain applied in the parent frame), and
 //       the joints' anchors / axes in the parent frame;
@@ -1323,11 +1346,9 @@ template <typename T, int G> MJB_DEV void kinematics(Ctx<T>& c) {
   MJB_ENV(c); T* w = c.w; const int lane = c.lane;
   T *xpos = w + L.xpos, *xquat = w + L.xquat, *xmat = w + L.xmat, *xipos = w + L.xipos, *ximat = w + L.ximat;
   T *qpos = w + L.qpos, *xanchor = w + L.xanchor, *xaxis = w + L.xaxis;
-  if (lane == 0) {
-    xpos[0] = xpos[1] = xpos[2] = 0; xquat[0] = 1; xquat[1] = xquat[2] = xquat[3] = 0;
-    xipos[0] = xipos[1] = xipos[2] = 0;
+  if (lane == 0) {                                              // the world body's frame: in the overlay, so per step (world_body_consts has the rest)
 #pragma unroll
-    for (int k = 0; k < 9; k++) { xmat[k] = (k % 4 == 0) ? (T)1 : (T)0; ximat[k] = xmat[k]; }
+    for (int k = 0; k < 9; k++) xmat[k] = (k % 4 == 0) ? (T)1 : (T)0;
   }
   // (1) local poses; xpos/xquat/xanchor/xaxis temporarily hold parent-frame values
   for (int b = 1 + lane; b < m.nbody; b += G) {
@@ -1521,12 +1542,7 @@ template <typename T, int G> MJB_DEV void com_pos(Ctx<T>& c) {
   }
   gsync<G>();
   T* cin = w + L.cinert;
-  for (int b = lane; b < m.nbody; b += G) {
-    if (b == 0) {
-#pragma unroll
-      for (int k = 0; k < 10; k++) cin[k] = 0;
-      continue;
-    }
+  for (int b = 1 + lane; b < m.nbody; b += G) {                 // cinert of the world body: world_body_consts
     int r = m.body_rootid[b];
     T off[3], im[9], res[10];
     const T MJB_CONST* inertia = prm_row<PRM_BODY_INERTIA>(c, m.body_inertia, 3 * m.nbody);
@@ -1540,28 +1556,25 @@ template <typename T, int G> MJB_DEV void com_pos(Ctx<T>& c) {
     for (int k = 0; k < 10; k++) cin[10 * b + k] = res[k];
   }
   T *cdof = w + L.cdof, *xanchor = w + L.xanchor, *xaxis = w + L.xaxis;
-  for (int j = lane; j < m.njnt; j += G) {
-    int b = MJB_REC(m, jnt_irec, 6, j, 3), da = MJB_REC(m, jnt_irec, 6, j, 2), r = MJB_REC(m, jnt_irec, 6, j, 5), jt = MJB_REC(m, jnt_irec, 6, j, 0);
+  // one lane per DOF (a free joint's six dofs on six lanes, not a 3-trip loop on one): selects pick the axis - the joint's, or for
+  // a free joint world axis i (translations) and column i - 3 of the body's frame (rotations) - and whether the dof is a translation
+  // [0; axis] or a rotation [axis; axis x off]
+  for (int i = lane; i < m.nv; i += G) {
+    const int j = m.dof_jntid[i];
+    const int b = MJB_REC(m, jnt_irec, 6, j, 3), da = MJB_REC(m, jnt_irec, 6, j, 2), r = MJB_REC(m, jnt_irec, 6, j, 5), jt = MJB_REC(m, jnt_irec, 6, j, 0);
     T off[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) off[k] = sc[3 * r + k] - xanchor[3 * j + k];
-    T* cd = cdof + 6 * da;
-    if (jt == JNT_FREE) {
-      for (int i = 0; i < 3; i++) {
+    const int q = i - da;                                       // the dof's rank in its joint
+    const bool fre = jt == JNT_FREE, frot = fre && q >= 3, trans = jt == JNT_SLIDE || (fre && q < 3);
+    const T* src = frot ? xmat + 9 * b + (q - 3) : xaxis + 3 * j;
+    const int st = frot ? 3 : 1;
+    T ax[3] = {src[0], src[st], src[2 * st]}, cr[3];
+    if (fre && q < 3) { ax[0] = q == 0 ? (T)1 : (T)0; ax[1] = q == 1 ? (T)1 : (T)0; ax[2] = q == 2 ? (T)1 : (T)0; }
+    cross3(cr, ax, off);
+    T* cd = cdof + 6 * i;
 #pragma unroll
-        for (int k = 0; k < 6; k++) cd[6 * i + k] = (k == 3 + i) ? (T)1 : (T)0;
-        T ax[3] = {xmat[9 * b + i], xmat[9 * b + 3 + i], xmat[9 * b + 6 + i]}, cr[3];
-        cross3(cr, ax, off);
-        T* cc = cd + 6 * (3 + i);
-        cc[0] = ax[0]; cc[1] = ax[1]; cc[2] = ax[2]; cc[3] = cr[0]; cc[4] = cr[1]; cc[5] = cr[2];
-      }
-    } else if (jt == JNT_SLIDE) {
-      cd[0] = cd[1] = cd[2] = 0; cd[3] = xaxis[3 * j]; cd[4] = xaxis[3 * j + 1]; cd[5] = xaxis[3 * j + 2];
-    } else {
-      T ax[3] = {xaxis[3 * j], xaxis[3 * j + 1], xaxis[3 * j + 2]}, cr[3];
-      cross3(cr, ax, off);
-      cd[0] = ax[0]; cd[1] = ax[1]; cd[2] = ax[2]; cd[3] = cr[0]; cd[4] = cr[1]; cd[5] = cr[2];
-    }
+    for (int k = 0; k < 3; k++) { cd[k] = trans ? (T)0 : ax[k]; cd[3 + k] = trans ? ax[k] : cr[k]; }
   }
   // fixed tendons: length (their Jacobian holds model constants only: tendon_jacobian, once per launch)
   T *tl = w + L.ten_length, *qpos = w + L.qpos;
@@ -2094,7 +2107,7 @@ template <typename T, int G> MJB_DEV void vel_bias_passive(Ctx<T>& c) {
   T *qvel = w + L.qvel, *qpos = w + L.qpos;
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 6; k++) { cvel[k] = 0; cfrc[k] = 0; }
+    for (int k = 0; k < 6; k++) cfrc[k] = 0;                   // (cvel of the world body: world_body_consts)
     const T MJB_CONST* gravity = prm_row<PRM_GRAVITY>(c, m.gravity, 3);
     cacc[0] = cacc[1] = cacc[2] = 0; cacc[3] = -gravity[0]; cacc[4] = -gravity[1]; cacc[5] = -gravity[2];
   }
@@ -2698,15 +2711,37 @@ MJB_DEV unsigned philox_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3
   }
   return c0;
 }
-template <typename T, int G> MJB_DEV void random_ctrl(ModelRef<T> m, T* ctrl, unsigned seed, unsigned env, unsigned step, T scale, int lane) {
-  for (int a = lane; a < m.nu; a += G) {
-    unsigned r = philox_first(env, step, (unsigned)a, 0u, seed, 0x5EEDu);
-    T u = (T)(r >> 8) * (T)(1.0 / 16777216.0);
-    T lo = -1, hi = 1;
-    if (m.actuator_ctrllimited[a]) { lo = MJB_REC(m, actuator_ctrlrange, 2, a, 0); hi = MJB_REC(m, actuator_ctrlrange, 2, a, 1); }
-    ctrl[a] = (T)0.5 * (lo + hi) + (T)0.5 * (hi - lo) * scale * (2 * u - 1);
-  }
+// the control of actuator a at (global environment, global step): a pure function of its arguments, never of the state
+template <typename T> MJB_DEV T random_ctrl_value(ModelRef<T> m, unsigned seed, unsigned env, unsigned step, int a, T scale) {
+  unsigned r = philox_first(env, step, (unsigned)a, 0u, seed, 0x5EEDu);
+  T u = (T)(r >> 8) * (T)(1.0 / 16777216.0);
+  T lo = -1, hi = 1;
+  if (m.actuator_ctrllimited[a]) { lo = MJB_REC(m, actuator_ctrlrange, 2, a, 0); hi = MJB_REC(m, actuator_ctrlrange, 2, a, 1); }
+  return (T)0.5 * (lo + hi) + (T)0.5 * (hi - lo) * scale * (2 * u - 1);
 }
+template <typename T, int G> MJB_DEV void random_ctrl(ModelRef<T> m, T* ctrl, unsigned seed, unsigned env, unsigned step, T scale, int lane) {
+  for (int a = lane; a < m.nu; a += G) ctrl[a] = random_ctrl_value<T>(m, seed, env, step, a, scale);
+}
+// The same stream, drawn for npass = G / nu consecutive steps in ONE Philox pass (a wave-wide instruction costs the same for nu
+// lanes as for G): lane l draws actuator l % nu of step `step + l / nu` and keeps it in `held`; `since` (group-uniform) counts the
+// steps served from the pass, and at each step the lane group [since nu, since nu + nu) stores its values - one predicated LDS
+// store.  A pass starts wherever the caller's first step is (since = npass forces the draw); steps drawn beyond the caller's last
+// one are dropped.  The state never enters, so a bad-state reset between two steps of a pass leaves the held values valid.
+// Callers take this path for 0 < nu <= G (npass >= 1), random_ctrl otherwise.
+template <typename T, int G> MJB_DEV void random_ctrl_pass(ModelRef<T> m, T* ctrl, unsigned seed, unsigned env, unsigned step, T scale, int lane, int npass, int& since, T& held) {
+  const int nu = m.nu;
+  if (since >= npass) {
+    since = 0;
+    const int j = lane / nu;
+    held = 0;
+    if (j < npass) held = random_ctrl_value<T>(m, seed, env, step + (unsigned)j, lane - j * nu, scale);
+  }
+  const unsigned a = (unsigned)(lane - since * nu);
+  if (a < (unsigned)nu) ctrl[a] = held;
+  since++;
+}
+// passes of random_ctrl_pass for a launch: 0 = the per-step draw
+MJB_DEV int random_ctrl_npass(int ctrl_mode, int nu, int G) { return ctrl_mode == CTRL_RANDOM && nu > 0 && nu <= G ? G / nu : 0; }
 
 // Linear state-feedback controller evaluated on the device (the LQR law of the reference's examples,
 // examples/humanoid/controllers/lqr.py:147-170): ctrl = clip(u0 - K dx), dx = [q (-) q0 ; qvel - v0] in tangent space.
@@ -2945,6 +2980,20 @@ template <typename TS> MJB_DEV void raise_engine_flags(DataRef<TS> d, int fl) {
 MJB_DEV unsigned xfer_dead_tag(unsigned tagbase) { return tagbase | 0xFFFFFu; }
 #endif
 
+// A value that every lane of the wavefront holds alike, moved to scalar registers.  With one environment per wavefront the clock of
+// the environment then does not occupy two vector registers through the whole step loop (256 of 256 in use, with spills): they pay
+// for the register in which random_ctrl_pass holds its draws.  Fewer lanes per environment: several clocks per wavefront, unchanged.
+template <int G> MJB_DEV double wave_uniform(double x) {
+#ifndef MJB_HOST_EMU
+  if constexpr (G == 64) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+  }
+#endif
+  return x;
+}
+
 // steps [s_begin, s_end) of the launch's a.nstep.  tag_in != 0: the state comes from the hand-over buffer (written by the wave that
 // ran the steps before s_begin).  s_end < a.nstep (ticket mode): it goes there; else to the state arrays, and this call ends the
 // launch for the environment (counters, kinematic outputs, dumps).
@@ -3013,16 +3062,22 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
   for (int i = lane; i < nu; i += G) w[L.ctrl + i] = a.ctrl_mode == CTRL_ZERO ? (T)0 : (T)d.ctrl[(size_t)env * nu + i];
   for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;       // structural zeros of the mass matrix (crb_factor fills the rest)
   tendon_jacobian<T, G>(c);
+  world_body_consts<T, G>(c);
 #ifndef MJB_HOST_EMU
   if (a.mirror && a.mirror_mask) mirror_in<T, G>(m, L, w, a.mirror, a.mirror_mask, env, d.batch, lane, time);
 #endif
+  time = wave_uniform<G>(time);
   int badqpos = 0, badqvel = 0, badqacc = 0;
+  const int ctrl_npass = a.mode == 0 ? random_ctrl_npass(a.ctrl_mode, nu, G) : 0;
+  int ctrl_since = ctrl_npass;                                  // the first step of this call (any s_begin) starts a pass of its own
+  T ctrl_held = 0;
   gsync<G>();
   MJB_STAMP_START(c);
   if (a.mode != 0) { s_begin = 0; s_end = 1; }
   c.skip_dynamics = a.mode == 2;
   MJB_SET_REPEAT(c, a.mode == 0 ? a.repeat_phase : -1);
   const int nstage = (a.mode == 0 && m.integrator == INT_RK4) ? 4 : 1;
+  int obs_left = a.obs_every > 0 ? a.obs_every - s_begin % a.obs_every : 0;   // steps until the next observation: a countdown carried across the steps, seeded once per call from its first step
 #ifndef MJB_HOST_EMU
   const unsigned hwslot = __builtin_amdgcn_s_getreg((3 << 11) | 4);      // HW_ID[3:0]: this wave's slot on its SIMD
 #endif
@@ -3040,7 +3095,13 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
       if (group_bad<T, G>(w + L.qpos, nq, lane)) { badqpos++; reset_state<T, G>(c); time = 0; }
       if (group_bad<T, G>(w + L.qvel, nv, lane)) { badqvel++; reset_state<T, G>(c); time = 0; }
       if (a.ctrl_mode == CTRL_RANDOM) {
-        for (int rp_ = MJB_REP_N(c, REP_CTRL); rp_ > 0; rp_--) random_ctrl<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane);
+        const int since0 = ctrl_since;                      // (diagnostic build: the repeated piece draws whenever the first one did)
+        for (int rp_ = MJB_REP_N(c, REP_CTRL); rp_ > 0; rp_--) {
+          if (ctrl_npass > 0) {
+            ctrl_since = since0;
+            random_ctrl_pass<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane, ctrl_npass, ctrl_since, ctrl_held);
+          } else random_ctrl<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane);
+        }
         gsync<G>();
       } else if (a.ctrl_mode == CTRL_FEEDBACK) feedback_ctrl<T, G>(c, a, a.env0 + (unsigned)env, a.step0 + (unsigned)s);
       else if (a.ctrl_mode == CTRL_SEQUENCE) {             // s: the launch-local step index, also in ticket mode
@@ -3063,8 +3124,9 @@ MJB_DEV void env_run(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, D
     if (nstage == 1) euler<T, G>(c);
     MJB_STAMP(c, PH_INTEG);
     if (tlacc) *tlacc += ((unsigned long long)(unsigned)c.niter << 8) | ((unsigned long long)(unsigned)c.nefc << 24) | ((unsigned long long)(unsigned)c.ncon << 44);
-    time += a.dt;
-    if (a.obs_every > 0 && ((s + 1) % a.obs_every) == 0) {
+    time = wave_uniform<G>(time + a.dt);
+    if (a.obs_every > 0 && --obs_left == 0) {                   // (s + 1) % obs_every == 0, without the division
+      obs_left = a.obs_every;
       size_t slot = (size_t)((s + 1) / a.obs_every - 1);
       write_obs<T, TS, G>(c, obs, time, obs_out + (slot * (size_t)d.batch + (size_t)env) * (size_t)obs.dim);
     }
@@ -3197,17 +3259,23 @@ MJB_DEV void env_run2(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, 
     for (int i = lane; i < nu; i += G) w[L.ctrl + i] = a.ctrl_mode == CTRL_ZERO ? (T)0 : (T)d.ctrl[(size_t)env * nu + i];
     for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;     // structural zeros of the mass matrix
     tendon_jacobian<T, G>(c);
+    world_body_consts<T, G>(c);
     if (lane < 8) mail[lane] = 0;
     time = d.time[env];
     if (a.mirror && a.mirror_mask) mirror_in<T, G>(m, L, w, a.mirror, a.mirror_mask, env, d.batch, lane, time);
   }
   __syncthreads();
+  const int ctrl_npass = random_ctrl_npass(a.ctrl_mode, nu, G);
+  int ctrl_since = ctrl_npass;                                  // wave 0's pass of random controls (random_ctrl_pass)
+  T ctrl_held = 0;
+  int obs_left = a.obs_every;                                   // steps until the next observation (wave 0 counts down)
   for (int s = 0; s < a.nstep; s++) {
     if (wv == 0) {
       if (group_bad<T, G>(w + L.qpos, nq, lane)) { badqpos++; reset_state<T, G>(c); time = 0; }
       if (group_bad<T, G>(w + L.qvel, nv, lane)) { badqvel++; reset_state<T, G>(c); time = 0; }
       if (a.ctrl_mode == CTRL_RANDOM) {
-        random_ctrl<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane);
+        if (ctrl_npass > 0) random_ctrl_pass<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane, ctrl_npass, ctrl_since, ctrl_held);
+        else random_ctrl<T, G>(m, w + L.ctrl, a.seed, a.env0 + (unsigned)env, a.step0 + (unsigned)s, (T)a.ctrl_scale, lane);
         gsync<G>();
       } else if (a.ctrl_mode == CTRL_FEEDBACK) feedback_ctrl<T, G>(c, a, a.env0 + (unsigned)env, a.step0 + (unsigned)s);
       else if (a.ctrl_mode == CTRL_SEQUENCE) {
@@ -3267,7 +3335,8 @@ MJB_DEV void env_run2(const DevModel<T> MJB_CONST* mp, const Lay MJB_CONST* lp, 
     __syncthreads();
     if (wv == 0) {
       time += a.dt;
-      if (a.obs_every > 0 && ((s + 1) % a.obs_every) == 0) {
+      if (a.obs_every > 0 && --obs_left == 0) {
+        obs_left = a.obs_every;
         size_t slot = (size_t)((s + 1) / a.obs_every - 1);
         write_obs<T, TS, G>(c, obs, time, obs_out + (slot * (size_t)d.batch + (size_t)env) * (size_t)obs.dim);
       }

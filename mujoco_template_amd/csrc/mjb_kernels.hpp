@@ -208,6 +208,7 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
   Ctx<T> c(mp, lp, w, wi, lane, kernarg_prm<T, TS>(), env);
   for (int i = lane; i < nv * nv; i += G) w[L.M + i] = 0;       // structural zeros of the mass matrix (crb_factor fills the rest)
   tendon_jacobian<T, G>(c);                                     // also for the jobs that skip the position stage
+  world_body_consts<T, G>(c);
   const int nstage = rk4 ? 4 : 1;
   for (int it = share > 0 ? -1 : 0; it < cnt; it++) {           // it = -1: the shared stages at the nominal state
     {                                                           // the point's rows: every column restarts from the same state and warm start
@@ -339,6 +340,7 @@ __global__ __launch_bounds__(64) void k_jac(const DevModel<T>* mg, const Lay* lg
   const int nq = m.nq, nv = m.nv;
   const T MJB_CONST* body_mass = prm_row<PRM_BODY_MASS>(c, m.body_mass, m.nbody);
   for (int i = lane; i < nq; i += G) w[L.qpos + i] = (T)d.qpos[(size_t)env * nq + i];
+  world_body_consts<T, G>(c);
   gsync<G>();
   kinematics<T, G>(c);
   com_pos<T, G>(c);
