@@ -309,6 +309,26 @@ int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step
 /* slabs the last mjb_transition_fd_points on this data object ran in (0: none yet) */
 int mjb_fd_points_slabs(const mjbData* d);
 
+/* ---- the sensor half of mjd_transitionFD: C = d sensordata / d[dq; dv], D = d sensordata / d ctrl, with ns = nsensordata rows.
+ * The reference passes None, None for them (mujoco_template/linearization.py:28-34); these two calls complete that call site for
+ * output-feedback design (observers, Kalman gains, LQG) on the device.  The sensordata differenced is what one step from each
+ * perturbed point leaves (mj_step: the sensors of its last forward pass), subtracted as it is - framequat rows get no quaternion
+ * treatment - under the rule of (A, B): centred where both nudges are valid, one-sided at a ctrlrange bound, inputs in the order
+ * dq | dv | ctrl.  (A, B) are bit for bit those of the calls above; the columns are the same launch, which also keeps every
+ * column's sensordata (ns float64 per column of scratch more), and one more small kernel differences them.
+ * mjb_transition_fd_sensors: the pinned-view form of mjb_transition_fd_pinned with C [batch, ns, 2nv] and D [batch, ns, nu] beside
+ * A and B (same validity, same zero-copy rule for small batches).  A model without sensors: *C_pinned = *D_pinned = NULL.
+ * mjb_transition_fd_points_sensors: mjb_transition_fd_points with C_dev [T, batch, ns, 2nv] and D_dev [T, batch, ns, nu], float64
+ * device memory of the caller checked like A_dev and B_dev; ns == 0 or nu == 0: nothing is written there and NULL is allowed.
+ * Slabs as above, the sensor scratch counted in the budget. ---- */
+int mjb_transition_fd_sensors(mjbData* d, double eps, int centered, const double** A_pinned, const double** B_pinned,
+                              const double** C_pinned, const double** D_pinned);
+int mjb_transition_fd_points_sensors(mjbData* d, int T, const void* qpos, long qpos_step_stride, long qpos_env_stride,
+                                     const void* qvel, long qvel_step_stride, long qvel_env_stride,
+                                     const void* ctrl, long ctrl_step_stride, long ctrl_env_stride,
+                                     const void* qacc_warmstart, long ws_step_stride, long ws_env_stride,
+                                     double eps, int centered, double* A_dev, double* B_dev, double* C_dev, double* D_dev);
+
 /* ---- batched LQR / iLQR on the arrays above: the backward (Riccati) recursion and the line search's candidate controls.  The
  * reference designs its controllers from ONE (A, B) with scipy.linalg.solve_discrete_are (examples/humanoid/controllers/lqr.py:114);
  * this is the finite-horizon, time-varying form of that recursion along a trajectory, fed by mjb_transition_fd_points.

@@ -27,7 +27,7 @@ from .rollout import linearize_rollout, rollout
 from .logging import DataProbe, StateControlRecorder
 from .runtime import StepHook, TrajectoryLogger, iterate_passive, run_passive_headless
 from .setpoints import SetpointResult, solve_setpoint, steady_ctrl0, steady_ctrl0_device
-from .trajopt import DareResult, LqrBackwardResult, LqrBoxResult, LyapResult, PolesResult, TrajCostResult, TrajSelectResult, lqr_backward, lqr_candidates, select_candidates, solve_dare, closed_loop_poles, closed_loop_cost, trajectory_cost
+from .trajopt import DareResult, KalmanResult, solve_kalman, LqrBackwardResult, LqrBoxResult, LyapResult, PolesResult, TrajCostResult, TrajSelectResult, lqr_backward, lqr_candidates, select_candidates, solve_dare, closed_loop_poles, closed_loop_cost, trajectory_cost
 
 __version__ = "0.1.0"
 
@@ -39,6 +39,6 @@ __all__ = [
     "compute_requested_jacobians", "StepHook", "iterate_passive", "run_passive_headless", "steady_ctrl0", "DataProbe",
     "StateControlRecorder", "TrajectoryLogger", "rollout", "linearize_rollout", "ObservationDict", "DeviceData", "uses_device_arrays",
     "ObservationArray", "Observation", "JacobianDict", "JacobiansDict", "InfoDict", "StateSnapshot", "lqr_backward", "lqr_candidates", "trajectory_cost", "select_candidates", "TrajCostResult", "TrajSelectResult",
-    "LqrBackwardResult", "LqrBoxResult", "solve_dare", "DareResult", "closed_loop_poles", "PolesResult", "closed_loop_cost", "LyapResult", "solve_setpoint", "steady_ctrl0_device", "SetpointResult",
+    "LqrBackwardResult", "LqrBoxResult", "solve_dare", "DareResult", "solve_kalman", "KalmanResult", "closed_loop_poles", "PolesResult", "closed_loop_cost", "LyapResult", "solve_setpoint", "steady_ctrl0_device", "SetpointResult",
     "feedback_ctrl", "rollout_feedback", "FeedbackRollout", "DeviceFeedbackController", "__version__",
 ]

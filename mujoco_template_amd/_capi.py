@@ -185,6 +185,10 @@ def load_library() -> ctypes.CDLL:
     L.mjb_transition_fd_points.restype = ci
     L.mjb_fd_points_slabs.argtypes = [vp]
     L.mjb_fd_points_slabs.restype = ci
+    L.mjb_transition_fd_sensors.argtypes = [vp, cd, ci] + [ctypes.POINTER(ctypes.POINTER(cd))] * 4
+    L.mjb_transition_fd_sensors.restype = ci
+    L.mjb_transition_fd_points_sensors.argtypes = [vp, ci, vp, cl, cl, vp, cl, cl, vp, cl, cl, vp, cl, cl, cd, ci, vp, vp, vp, vp]
+    L.mjb_transition_fd_points_sensors.restype = ci
     L.mjb_lqr_backward.argtypes = [vp, ctypes.POINTER(LqrBackwardStruct)]
     L.mjb_lqr_backward.restype = ci
     L.mjb_lqr_backward_box.argtypes = [vp, ctypes.POINTER(LqrBackwardBoxStruct)]
@@ -980,27 +984,44 @@ class BatchSim:
     def obs_gather(self, spec: ObsSpecHandle, out_ptr: int) -> None:
         _check(load_library().mjb_obs_gather(self.ptr, spec.ptr, ctypes.c_void_p(out_ptr)))
 
-    def transition_fd(self, eps: float = 1e-6, centered: bool = True, *, copy: bool = True) -> tuple[np.ndarray, np.ndarray]:
+    def transition_fd(self, eps: float = 1e-6, centered: bool = True, *, copy: bool = True, sensors: bool = False):
         """(A [batch, 2nv, 2nv], B [batch, 2nv, nu]).  ``copy=False`` returns views of the library's pinned result blocks (no
-        16 MB host copy at humanoid batch 512), valid until the next ``transition_fd`` on this object."""
+        16 MB host copy at humanoid batch 512), valid until the next ``transition_fd`` on this object.
+
+        ``sensors=True`` returns ``(A, B, C, D)`` with the sensor Jacobians ``C [batch, ns, 2nv] = d sensordata / d[dq; dv]`` and
+        ``D [batch, ns, nu] = d sensordata / d ctrl`` (``mjb_transition_fd_sensors``; ``ns = nsensordata``, empty for a model
+        without sensors): the same columns, ``A`` and ``B`` bitwise those of the plain call."""
         m = self.model.compiled
         if not self._fd_spec_tried:                                # first call: the per-model specialised kernel, by the same policy as the step kernel
             self._fd_spec_tried = True
             self._specialize_by_policy(self.specialize_fd, "finite-difference kernel", default=True)
         pa, pb = ctypes.POINTER(ctypes.c_double)(), ctypes.POINTER(ctypes.c_double)()
-        _check(load_library().mjb_transition_fd_pinned(self.ptr, float(eps), int(bool(centered)), ctypes.byref(pa), ctypes.byref(pb)))
+        if sensors:
+            pc, pd = ctypes.POINTER(ctypes.c_double)(), ctypes.POINTER(ctypes.c_double)()
+            _check(load_library().mjb_transition_fd_sensors(self.ptr, float(eps), int(bool(centered)), ctypes.byref(pa), ctypes.byref(pb),
+                                                             ctypes.byref(pc), ctypes.byref(pd)))
+        else:
+            _check(load_library().mjb_transition_fd_pinned(self.ptr, float(eps), int(bool(centered)), ctypes.byref(pa), ctypes.byref(pb)))
         A = np.ctypeslib.as_array(pa, shape=(self.batch, 2 * m.nv, 2 * m.nv))
         Bv = np.ctypeslib.as_array(pb, shape=(self.batch, 2 * m.nv, m.nu)) if m.nu else np.zeros((self.batch, 2 * m.nv, 0))
-        return (A.copy(), Bv.copy()) if copy else (A, Bv)
+        if not sensors:
+            return (A.copy(), Bv.copy()) if copy else (A, Bv)
+        ns = m.nsensordata
+        C = np.ctypeslib.as_array(pc, shape=(self.batch, ns, 2 * m.nv)) if ns else np.zeros((self.batch, 0, 2 * m.nv))
+        D = np.ctypeslib.as_array(pd, shape=(self.batch, ns, m.nu)) if ns and m.nu else np.zeros((self.batch, ns, m.nu))
+        return (A.copy(), Bv.copy(), C.copy(), D.copy()) if copy else (A, Bv, C, D)
 
-    def transition_fd_points(self, qpos, qvel, ctrl, qacc_warmstart=None, *, eps: float = 1e-6, centered: bool = True, out=None):
+    def transition_fd_points(self, qpos, qvel, ctrl, qacc_warmstart=None, *, eps: float = 1e-6, centered: bool = True, out=None,
+                             sensors: bool = False):
         """Finite-difference transition matrices at caller-chosen points (``mjb_transition_fd_points``): ``qpos [T, B, nq]``,
         ``qvel [T, B, nv]``, ``ctrl [T, B, nu]`` and ``qacc_warmstart [T, B, nv]`` (``None`` = zeros) are torch tensors on this
         object's GPU in the data's dtype, or ``[B, n]`` for one point per environment.  Their own strides address them: column views
         of a rollout ring and ``expand``-ed tensors are read in place.  Returns ``(A [T, B, 2nv, 2nv], B [T, B, 2nv, nu])`` float64 on
         the GPU (without the leading axis for ``[B, n]`` inputs), or fills ``out=(A, B)``.  Block ``(t, e)`` is bitwise what
         ``transition_fd`` gives for environment ``e`` with the data's rows set to point ``(t, e)``; the data's own state is not
-        touched.  Enqueued on torch's current stream, nothing waits for the GPU; the inputs are kept referenced until the next call."""
+        touched.  Enqueued on torch's current stream, nothing waits for the GPU; the inputs are kept referenced until the next call.
+        ``sensors=True`` (``mjb_transition_fd_points_sensors``) returns, or fills in ``out``, ``(A, B, C [T, B, ns, 2nv], D [T, B, ns, nu])``
+        with the sensor Jacobians of ``transition_fd(sensors=True)``; ``A`` and ``B`` are bitwise those of the plain call."""
         import torch
 
         m = self.model.compiled
@@ -1038,12 +1059,15 @@ class BatchSim:
         ndim, T = lead
         if T < 1:
             raise ConfigError("transition_fd_points: T must be >= 1")
+        ns = m.nsensordata
+        shapes = [("A", (T, B, nx, nx)), ("B", (T, B, nx, nu))] + ([("C", (T, B, ns, nx)), ("D", (T, B, ns, nu))] if sensors else [])
         if out is None:
-            A = torch.empty((T, B, nx, nx), device=dev, dtype=torch.float64)
-            Bm = torch.empty((T, B, nx, nu), device=dev, dtype=torch.float64)
+            res = [torch.empty(shape, device=dev, dtype=torch.float64) for _, shape in shapes]
         else:
-            A, Bm = out
-            for name, x, shape in (("A", A, (T, B, nx, nx)), ("B", Bm, (T, B, nx, nu))):
+            res = list(out)
+            if len(res) != len(shapes):
+                raise ConfigError(f"transition_fd_points: out must be ({', '.join(n for n, _ in shapes)})")
+            for (name, shape), x in zip(shapes, res):
                 if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device != dev or not x.is_contiguous() or \
                         tuple(x.shape) not in (shape, shape[1:] if ndim == 2 else shape):
                     raise ConfigError(f"transition_fd_points: out {name} must be a contiguous float64 tensor {list(shape)} on {dev}")
@@ -1051,13 +1075,12 @@ class BatchSim:
             self._fd_spec_tried = True
             self._specialize_by_policy(self.specialize_fd, "finite-difference kernel", default=True)
         self.use_torch_stream()
-        self._fd_points_keep = (keep, A, Bm)                        # alive at least until the next call on this object
-        _check(load_library().mjb_transition_fd_points(self.ptr, T, *args, float(eps), int(bool(centered)),
-                                                        ctypes.c_void_p(A.data_ptr()) if A.numel() else None,
-                                                        ctypes.c_void_p(Bm.data_ptr()) if Bm.numel() else None))
+        self._fd_points_keep = (keep, res)                          # alive at least until the next call on this object
+        fn = load_library().mjb_transition_fd_points_sensors if sensors else load_library().mjb_transition_fd_points
+        _check(fn(self.ptr, T, *args, float(eps), int(bool(centered)), *[ctypes.c_void_p(x.data_ptr()) if x.numel() else None for x in res]))
         if out is not None:
-            return A, Bm
-        return (A[0], Bm[0]) if ndim == 2 else (A, Bm)
+            return tuple(res)
+        return tuple(x[0] for x in res) if ndim == 2 else tuple(res)
 
     def fd_points_slabs(self) -> int:
         """Slabs the last ``transition_fd_points`` ran in (``mjb_fd_points_slabs``)."""

@@ -126,6 +126,10 @@ struct mjbData {
   hipStream_t fd_stream = nullptr; bool fd_pending = false;
   int last_fd_slabs = 0;                                       // slabs of the last mjb_transition_fd_points (mjb_fd_points_slabs)
   Buffer<double> fd_A_host{Mem::Pinned}, fd_B_host{Mem::Pinned};   // the (A, B) blocks leave the device in one async copy each
+  // the sensor half (mjb_transition_fd_sensors / _points_sensors), made by the first call that asks for it: fd_s [npoint, ncol, ns] = the
+  // per-column sensordata beside fd_y, (C, D) result blocks as (A, B)
+  Buffer<double> fd_s, fd_C, fd_D, fd_C_host{Mem::Pinned}, fd_D_host{Mem::Pinned};
+  bool spec_fd_sensors = false;                                // the loaded MJB_KERNEL_FD code object knows FdPoints::sens_out (mjb_kernel_load)
   // mjb_jac: persistent buffers (grown on demand) - the request (kinds | ids) in pinned memory the kernel reads directly, the result
   // blocks pinned (small requests: written by the kernel itself) and on the device (large requests: one async copy each)
   Buffer<unsigned char> io_pin{Mem::Pinned};                   // pinned staging of mjb_get_array / mjb_set_array (grown on demand, with slack)
@@ -567,6 +571,8 @@ std::string spec_source(const HostModel& h_model, const Config& c, int dtype, in
   s += kind != MJB_KERNEL_FD ? baked_model_source<float>(h, ncon_max, nefc_max, prm_mask) : baked_model_source<double>(h, ncon_max, nefc_max, prm_mask);
   s += "#include \"mjb_kernels.hpp\"\n";
   if (prm_mask) s += "extern \"C\" __constant__ int mjb_spec_params = " + std::to_string(prm_mask) + ";   // checked by mjb_kernel_load\n";
+  // the point table's layout the kernel was compiled against, from the header itself: read by mjb_kernel_load
+  if (kind == MJB_KERNEL_FD) s += "extern \"C\" __constant__ int mjb_spec_fd_points = MJB_FD_POINTS_ABI;\n";
   return s;
 }
 
@@ -1000,6 +1006,15 @@ int mjb_kernel_load(mjbData* d, int kind, const void* image, long nbytes) {
     (void)hipModuleUnload(mod);
     return fail(MJB_ERR_ARG, "the specialised kernel was built for per-environment parameters " + std::to_string(built_for) + ", this data object has " +
                                  std::to_string(d->prm_mask) + " (take the source from mjb_kernel_source after mjb_set_env_param)");
+  }
+  if (kind == MJB_KERNEL_FD) {
+    // a code object from a header whose point table had no sensor output carries no such record (or an older one): it still serves
+    // the plain calls (the members it reads kept their offsets), and a sensor request takes the generic kernel instead (fd_run_slab)
+    int abi = 0;
+    if (hipModuleGetGlobal(&sym, &symsize, mod, "mjb_spec_fd_points") == hipSuccess && symsize == sizeof(int)) {
+      if (hipMemcpyDtoH(&abi, sym, sizeof(int)) != hipSuccess) { (void)hipModuleUnload(mod); return fail(MJB_ERR_DEVICE, "reading mjb_spec_fd_points of the code object failed"); }
+    } else (void)hipGetLastError();
+    d->spec_fd_sensors = abi == MJB_FD_POINTS_ABI;
   }
   d->spec[kind].mod = mod; d->spec[kind].fn = fn; d->spec_prm[kind] = built_for;
   if (kind == MJB_KERNEL_STEP) d->step_slots = -1;
@@ -1482,13 +1497,14 @@ int mjb_obs_gather(mjbData* d, const mjbObsSpec* s, void* out_dev) {
 static const unsigned long long kFdSlabBytes = 128ull << 20;
 
 // fd_y / fd_valid for `npoint` points: allocated once per data object and grown only when a larger slab comes
-static int fd_scratch(mjbData* d, size_t npoint, int ncol) {
+// (fd_s, the per-column sensordata, only for a call that asks for the sensor Jacobians)
+static int fd_scratch(mjbData* d, size_t npoint, int ncol, bool sensors = false) {
   const HostModel& h = d->model->h;
-  const size_t ny = npoint * ncol * (size_t)(h.nq + h.nv), nvalid = npoint * ncol;
-  if (ny <= d->fd_y.count() && nvalid <= d->fd_valid.count()) return MJB_OK;
+  const size_t ny = npoint * ncol * (size_t)(h.nq + h.nv), nvalid = npoint * ncol, ns = sensors ? npoint * ncol * (size_t)h.nsensordata : 0;
+  if (ny <= d->fd_y.count() && nvalid <= d->fd_valid.count() && ns <= d->fd_s.count()) return MJB_OK;
   // reserve releases the old blocks through hipFree, which waits for the kernels that may still read them
-  if (d->fd_y.reserve(ny) != hipSuccess || d->fd_valid.reserve(nvalid) != hipSuccess) {
-    (void)hipGetLastError(); reset_all(d->fd_y, d->fd_valid);
+  if (d->fd_y.reserve(ny) != hipSuccess || d->fd_valid.reserve(nvalid) != hipSuccess || (ns > 0 && d->fd_s.reserve(ns) != hipSuccess)) {
+    (void)hipGetLastError(); reset_all(d->fd_y, d->fd_valid, d->fd_s);
     return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
   }
   return MJB_OK;
@@ -1508,10 +1524,14 @@ static int fd_order_end(mjbData* d) {
 }
 
 // One slab of points (pt.p0, pt.npoint set): the column kernel, then the combine kernel into the slab's (A, B) blocks; enqueued only.
-static int fd_run_slab(mjbData* d, const FdPoints& pt, double eps, int centered, double* A, double* B) {
+// C non-null (nsensordata > 0): the column kernel also keeps every column's sensordata, and a second combine kernel writes the slab's (C, D).
+static int fd_run_slab(mjbData* d, const FdPoints& pt_in, double eps, int centered, double* A, double* B, double* C = nullptr, double* D = nullptr) {
   const HostModel& h = d->model->h;
   const int nin = 2 * h.nv + h.nu, ncol = 1 + 2 * nin;
-  { int rc = fd_scratch(d, (size_t)pt.npoint, ncol); if (rc != MJB_OK) return rc; }
+  const bool sensors = C != nullptr && h.nsensordata > 0;
+  { int rc = fd_scratch(d, (size_t)pt_in.npoint, ncol, sensors); if (rc != MJB_OK) return rc; }
+  FdPoints pt = pt_in;
+  pt.sens_out = sensors ? d->fd_s.get() : nullptr;
   // columns per job (k_fd shares the stages a chunk of columns cannot change), sized by the points of THIS launch
   int chunk;
   {
@@ -1525,7 +1545,9 @@ static int fd_run_slab(mjbData* d, const FdPoints& pt, double eps, int centered,
     if (chunk < 1) chunk = 1;
   }
   hipError_t e;
-  if (d->spec[MJB_KERNEL_FD].fn) {                              // per-model specialised kernel: same arguments, same grid as launch_fd_g
+  // per-model specialised kernel: same arguments, same grid as launch_fd_g.  A code object compiled before the point table had a sensor
+  // output (mjb_kernel_load) would not store the sensors: such a request runs on the generic kernel, whose results are the same
+  if (d->spec[MJB_KERNEL_FD].fn && (!sensors || d->spec_fd_sensors)) {
     const int epb = 64 / d->cfg.G_fd;
     const int njob = (1 + 2 * h.nu + chunk - 1) / chunk + (2 * h.nv + chunk - 1) / chunk + 2 * h.nv;
     const long ngroups = (long)pt.npoint * njob;
@@ -1542,10 +1564,15 @@ static int fd_run_slab(mjbData* d, const FdPoints& pt, double eps, int centered,
   hipLaunchKernelGGL(k_fd_combine<double>, dim3((unsigned)((nthreads + 127) / 128)), dim3(128), 0, d->stream, (const DevModel<double>*)d->md_dev, pt.npoint, ncol, centered, eps,
                      (const double*)d->fd_y.get(), (const int*)d->fd_valid.get(), A, B);
   HIPCHK(hipGetLastError());
+  if (sensors) {
+    hipLaunchKernelGGL(k_fd_combine_sensors<double>, dim3((unsigned)((nthreads + 127) / 128)), dim3(128), 0, d->stream, (const DevModel<double>*)d->md_dev, pt.npoint, ncol, centered,
+                       eps, (const double*)d->fd_s.get(), (const int*)d->fd_valid.get(), C, D);
+    HIPCHK(hipGetLastError());
+  }
   return MJB_OK;
 }
 
-static int transition_fd_impl(mjbData* d, double eps, int centered) {
+static int transition_fd_impl(mjbData* d, double eps, int centered, bool sensors = false) {
   if (!d) return fail(MJB_ERR_ARG, "NULL argument");
   if (!(eps > 0)) return fail(MJB_ERR_ARG, "eps must be > 0");
   const HostModel& h = d->model->h;
@@ -1559,6 +1586,13 @@ static int transition_fd_impl(mjbData* d, double eps, int centered) {
     reset_all(d->fd_A, d->fd_B, d->fd_A_host, d->fd_B_host);
     return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
   }
+  const size_t ns = (size_t)h.nsensordata, nC = B * ns * nx, nD = B * ns * (h.nu > 0 ? h.nu : 1);
+  sensors = sensors && ns > 0;
+  if (sensors && (reserve_zeroed(d->fd_C, nC) != hipSuccess || reserve_zeroed(d->fd_D, nD) != hipSuccess ||
+                  d->fd_C_host.reserve(nC) != hipSuccess || d->fd_D_host.reserve(nD) != hipSuccess)) {
+    reset_all(d->fd_C, d->fd_D, d->fd_C_host, d->fd_D_host);
+    return fail(MJB_ERR_DEVICE, "device allocation of FD scratch failed");
+  }
   // the point table of T = 1 over the data's own arrays: point e = environment e, one slab
   FdPoints pt;
   std::memset(&pt, 0, sizeof(pt));
@@ -1568,12 +1602,17 @@ static int transition_fd_impl(mjbData* d, double eps, int centered) {
   pt.p0 = 0; pt.npoint = d->batch;
   // a few environments (the reference's batch-1 loops with needs_linearization controllers): the combine kernel writes (A, B) straight
   // into the pinned result blocks (device-visible) - no staging copies; larger batches keep the device blocks + one async copy each
+  // (the rule looks at (A, B) alone, so that asking for the sensors does not move them)
   const bool zero_copy = B * nx * (nx + (size_t)h.nu) * sizeof(double) <= (size_t)256 * 1024;
   { int rc = fd_order_begin(d); if (rc != MJB_OK) return rc; }
-  { int rc = fd_run_slab(d, pt, eps, centered, zero_copy ? d->fd_A_host.get() : d->fd_A.get(), zero_copy ? d->fd_B_host.get() : d->fd_B.get()); if (rc != MJB_OK) return rc; }
+  { int rc = fd_run_slab(d, pt, eps, centered, zero_copy ? d->fd_A_host.get() : d->fd_A.get(), zero_copy ? d->fd_B_host.get() : d->fd_B.get(),
+                         !sensors ? nullptr : zero_copy ? d->fd_C_host.get() : d->fd_C.get(), !sensors ? nullptr : zero_copy ? d->fd_D_host.get() : d->fd_D.get());
+    if (rc != MJB_OK) return rc; }
   if (!zero_copy) {
     HIPCHK(hipMemcpyAsync(d->fd_A_host.get(), d->fd_A.get(), B * nx * nx * sizeof(double), hipMemcpyDeviceToHost, d->stream));
     if (h.nu > 0) HIPCHK(hipMemcpyAsync(d->fd_B_host.get(), d->fd_B.get(), B * nx * h.nu * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if (sensors) HIPCHK(hipMemcpyAsync(d->fd_C_host.get(), d->fd_C.get(), B * ns * nx * sizeof(double), hipMemcpyDeviceToHost, d->stream));
+    if (sensors && h.nu > 0) HIPCHK(hipMemcpyAsync(d->fd_D_host.get(), d->fd_D.get(), B * ns * h.nu * sizeof(double), hipMemcpyDeviceToHost, d->stream));
   }
   HIPCHK(hipStreamSynchronize(d->stream));
   d->fd_pending = false;                                       // this stream has drained, and every earlier FD launch was ordered before it
@@ -1595,11 +1634,11 @@ static int check_fd_array(const mjbData* d, const char* what, const void* ptr, b
   return why ? fail(MJB_ERR_ARG, pre + msg[why]) : MJB_OK;
 }
 
-int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step_stride, long qpos_env_stride,
-                             const void* qvel, long qvel_step_stride, long qvel_env_stride,
-                             const void* ctrl, long ctrl_step_stride, long ctrl_env_stride,
-                             const void* qacc_warmstart, long ws_step_stride, long ws_env_stride,
-                             double eps, int centered, double* A_dev, double* B_dev) {
+static int transition_fd_points_impl(mjbData* d, int T, const void* qpos, long qpos_step_stride, long qpos_env_stride,
+                                     const void* qvel, long qvel_step_stride, long qvel_env_stride,
+                                     const void* ctrl, long ctrl_step_stride, long ctrl_env_stride,
+                                     const void* qacc_warmstart, long ws_step_stride, long ws_env_stride,
+                                     double eps, int centered, double* A_dev, double* B_dev, bool sensors, double* C_dev, double* D_dev) {
   if (!d) return fail(MJB_ERR_ARG, "data is NULL");
   if (T < 1) return fail(MJB_ERR_ARG, "mjb_transition_fd_points: T must be >= 1");
   if (!(eps > 0)) return fail(MJB_ERR_ARG, "eps must be > 0");
@@ -1616,6 +1655,12 @@ int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step
   if ((rc = check_fd_array(d, "qacc_warmstart", qacc_warmstart, true, T, h.nv, ws_step_stride, ws_env_stride, es)) != MJB_OK) return rc;
   if ((rc = check_fd_array(d, "A_dev", A_dev, false, T, nx * nx, (long)d->batch * nx * nx, nx * nx, 8)) != MJB_OK) return rc;
   if ((rc = check_fd_array(d, "B_dev", B_dev, false, T, nx * h.nu, (long)d->batch * nx * h.nu, nx * h.nu, 8)) != MJB_OK) return rc;
+  const long ns = h.nsensordata;
+  if (sensors) {
+    if ((rc = check_fd_array(d, "C_dev", C_dev, false, T, ns * nx, (long)d->batch * ns * nx, ns * nx, 8)) != MJB_OK) return rc;
+    if ((rc = check_fd_array(d, "D_dev", D_dev, false, T, ns * h.nu, (long)d->batch * ns * h.nu, ns * h.nu, 8)) != MJB_OK) return rc;
+    sensors = ns > 0;                                           // no sensors in the model: nothing to write, the plain call
+  }
   if ((rc = refresh_options(d)) != MJB_OK) return rc;
   FdPoints pt;
   std::memset(&pt, 0, sizeof(pt));
@@ -1624,21 +1669,40 @@ int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step
   pt.ctrl_ss = ctrl_step_stride; pt.ctrl_es = ctrl_env_stride; pt.ws_ss = ws_step_stride; pt.ws_es = ws_env_stride;
   unsigned long long budget = kFdSlabBytes;
   if (const char* e = std::getenv("MJB_FD_SLAB_BYTES")) { const long long v = std::atoll(e); if (v > 0) budget = (unsigned long long)v; }
-  const long per_slab = fd_slab_points(fd_point_scratch_bytes(h.nq, h.nv, h.nu), budget);
+  const long per_slab = fd_slab_points(fd_point_scratch_bytes(h.nq, h.nv, h.nu, sensors ? h.nsensordata : 0), budget);
   const long nslab = fd_slab_count(npoint, per_slab);
   // the scratch of the largest slab, once, before anything is launched: growing it (the first call included) frees the old block, and
   // hipFree waits for the device - the one case in which this call synchronises
-  if ((rc = fd_scratch(d, (size_t)(npoint < per_slab ? npoint : per_slab), 1 + 2 * (2 * h.nv + h.nu))) != MJB_OK) return rc;
+  if ((rc = fd_scratch(d, (size_t)(npoint < per_slab ? npoint : per_slab), 1 + 2 * (2 * h.nv + h.nu), sensors)) != MJB_OK) return rc;
   if ((rc = fd_order_begin(d)) != MJB_OK) return rc;
   for (long k = 0; k < nslab; k++) {                            // slab after slab on the stream: the scratch is reused in stream order
     long p0 = 0, n = 0;
     fd_slab(npoint, per_slab, k, p0, n);
     pt.p0 = (int)p0; pt.npoint = (int)n;
-    rc = fd_run_slab(d, pt, eps, centered, A_dev + (size_t)p0 * nx * nx, B_dev ? B_dev + (size_t)p0 * nx * h.nu : nullptr);
+    rc = fd_run_slab(d, pt, eps, centered, A_dev + (size_t)p0 * nx * nx, B_dev ? B_dev + (size_t)p0 * nx * h.nu : nullptr,
+                     sensors ? C_dev + (size_t)p0 * ns * nx : nullptr, sensors && D_dev ? D_dev + (size_t)p0 * ns * h.nu : nullptr);
     if (rc != MJB_OK) return rc;
   }
   d->last_fd_slabs = (int)nslab;
   return fd_order_end(d);
+}
+
+int mjb_transition_fd_points(mjbData* d, int T, const void* qpos, long qpos_step_stride, long qpos_env_stride,
+                             const void* qvel, long qvel_step_stride, long qvel_env_stride,
+                             const void* ctrl, long ctrl_step_stride, long ctrl_env_stride,
+                             const void* qacc_warmstart, long ws_step_stride, long ws_env_stride,
+                             double eps, int centered, double* A_dev, double* B_dev) {
+  return transition_fd_points_impl(d, T, qpos, qpos_step_stride, qpos_env_stride, qvel, qvel_step_stride, qvel_env_stride, ctrl, ctrl_step_stride, ctrl_env_stride,
+                                   qacc_warmstart, ws_step_stride, ws_env_stride, eps, centered, A_dev, B_dev, false, nullptr, nullptr);
+}
+
+int mjb_transition_fd_points_sensors(mjbData* d, int T, const void* qpos, long qpos_step_stride, long qpos_env_stride,
+                                     const void* qvel, long qvel_step_stride, long qvel_env_stride,
+                                     const void* ctrl, long ctrl_step_stride, long ctrl_env_stride,
+                                     const void* qacc_warmstart, long ws_step_stride, long ws_env_stride,
+                                     double eps, int centered, double* A_dev, double* B_dev, double* C_dev, double* D_dev) {
+  return transition_fd_points_impl(d, T, qpos, qpos_step_stride, qpos_env_stride, qvel, qvel_step_stride, qvel_env_stride, ctrl, ctrl_step_stride, ctrl_env_stride,
+                                   qacc_warmstart, ws_step_stride, ws_env_stride, eps, centered, A_dev, B_dev, true, C_dev, D_dev);
 }
 
 int mjb_fd_points_slabs(const mjbData* d) { return d ? d->last_fd_slabs : -1; }
@@ -2087,6 +2151,16 @@ int mjb_transition_fd_pinned(mjbData* d, double eps, int centered, const double*
   int rc = transition_fd_impl(d, eps, centered);
   if (rc != MJB_OK) return rc;
   *A_pinned = d->fd_A_host.get(); *B_pinned = d->fd_B_host.get();
+  return MJB_OK;
+}
+
+int mjb_transition_fd_sensors(mjbData* d, double eps, int centered, const double** A_pinned, const double** B_pinned, const double** C_pinned, const double** D_pinned) {
+  if (!d || !A_pinned || !B_pinned || !C_pinned || !D_pinned) return fail(MJB_ERR_ARG, "NULL argument");
+  int rc = transition_fd_impl(d, eps, centered, true);
+  if (rc != MJB_OK) return rc;
+  const bool any = d->model->h.nsensordata > 0;                // a model without sensors: empty blocks, NULL
+  *A_pinned = d->fd_A_host.get(); *B_pinned = d->fd_B_host.get();
+  *C_pinned = any ? d->fd_C_host.get() : nullptr; *D_pinned = any ? d->fd_D_host.get() : nullptr;
   return MJB_OK;
 }
 

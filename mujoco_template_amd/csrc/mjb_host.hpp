@@ -452,9 +452,10 @@ inline bool fd_extent_inside(unsigned long long ptr, __int128 hi, unsigned long 
   const __int128 end = (__int128)ptr + (hi + 1) * (__int128)esize, limit = (__int128)base + (__int128)size;
   return ptr >= base && end <= limit;
 }
-// Scratch of one point: the next states of its 1 + 2 (2 nv + nu) columns, float64
-inline unsigned long long fd_point_scratch_bytes(int nq, int nv, int nu) {
-  return (unsigned long long)(1 + 2 * (2 * nv + nu)) * (unsigned long long)(nq + nv) * 8ull;
+// Scratch of one point: the next states of its 1 + 2 (2 nv + nu) columns, float64 - and, when the sensor Jacobians are asked for, the
+// nsens = nsensordata sensor values of every column beside them (fd_s)
+inline unsigned long long fd_point_scratch_bytes(int nq, int nv, int nu, int nsens = 0) {
+  return (unsigned long long)(1 + 2 * (2 * nv + nu)) * (unsigned long long)(nq + nv + (nsens > 0 ? nsens : 0)) * 8ull;
 }
 // Points per slab under a scratch budget: as many as fit, at least one (a point larger than the budget still runs, alone)
 inline long fd_slab_points(unsigned long long bytes_per_point, unsigned long long budget) {

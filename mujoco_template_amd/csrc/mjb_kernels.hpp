@@ -179,7 +179,11 @@ static_assert(offsetof(FkaDF, ncol) == offsetof(FkaDF, d) + sizeof(DevData<float
               offsetof(FkaDF, cv) == offsetof(FkaDF, valid) + 8 && offsetof(FkaDF, cc) == offsetof(FkaDF, cv) + 4 &&
               offsetof(FkaDF, pt) == offsetof(FkaDF, cc) + 4, "(ncol, eps, y_out, valid, cv, cc, pt) follow d without padding beyond ncol's");
 static_assert(sizeof(DevData<float>) == sizeof(DevData<double>) && offsetof(FkaDD, pt) == offsetof(FkaDF, pt) && alignof(FdPoints) == 8 &&
-              sizeof(FkaDF) == offsetof(FkaDF, pt) + sizeof(FdPoints) && sizeof(FdPoints) == 12 * 8 + 2 * 4, "the point table is the last kernel argument");
+              sizeof(FkaDF) == offsetof(FkaDF, pt) + sizeof(FdPoints) && sizeof(FdPoints) == 13 * 8 + 2 * 4, "the point table is the last kernel argument");
+static_assert(offsetof(FdPoints, p0) == 12 * 8 && offsetof(FdPoints, sens_out) == 13 * 8, "the sensor output is the table's last member: the others keep their offsets");
+// Layout revision of FdPoints.  A specialised FD translation unit records the one it was compiled against (mjb_spec_fd_points, spec_source):
+// a code object without that record has no sensor member and is never launched with a sensor output (mjb_kernel_load, fd_run_slab)
+#define MJB_FD_POINTS_ABI 2
 
 template <typename T, typename TS, int G>
 MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& d, int ncol, T eps, T* y_out, int* valid, int cv, int cc) {
@@ -265,6 +269,11 @@ MJB_DEV void k_fd_body(const DevModel<T>* mg, const Lay* lg, const DevData<TS>& 
     for (int i = lane; i < nq; i += G) y[i] = w[L.qpos + i];
     for (int i = lane; i < nv; i += G) y[nq + i] = w[L.qvel + i];
     if (lane == 0) valid[slot] = ok;
+    // the sensordata a step from this column's point leaves (k_step: the last forward pass's, so RK4's fourth stage): the integrators do not touch it
+    if (pt.sens_out) {
+      double* so = pt.sens_out + slot * m.nsensordata;
+      for (int i = lane; i < m.nsensordata; i += G) so[i] = (double)w[L.sens + i];
+    }
     gsync<G>();
   }
 }
@@ -320,6 +329,34 @@ __global__ void k_fd_combine(const DevModel<T>* mg, int batch, int ncol, int cen
   for (int r = 0; r < nv; r++) {
     T dv = (b[nq + r] - a[nq + r]) / den;
     if (k < 2 * nv) Ae[(size_t)(nv + r) * nx + k] = dv; else Be[(size_t)(nv + r) * nu + (k - 2 * nv)] = dv;
+  }
+}
+
+// The sensor half of mjd_transitionFD (the reference passes None, None for it, mujoco_template/linearization.py:28-34):
+// C = d sensordata / d[dq;dv]  (ns x 2nv), D = d sensordata / dctrl (ns x nu), ns = nsensordata, row-major per point, from the per-column
+// sensor vectors s [batch, ncol, ns] of k_fd (FdPoints::sens_out).  One thread per (point, input k), k_fd_combine's rule per input:
+// centred where both sides are valid, one-sided where one is, 0 where none.  Plain differences: framequat rows are subtracted as they are.
+template <typename T>
+__global__ void k_fd_combine_sensors(const DevModel<T>* mg, int batch, int ncol, int centered, T eps, const T* s, const int* valid, T* C, T* D) {
+  ModelRef<T> m = *(const DevModel<T> MJB_CONST*)mg;
+  const int nv = m.nv, nu = m.nu, ns = m.nsensordata, nin = 2 * nv + nu, nx = 2 * nv;
+  long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid >= (long)batch * nin) return;
+  int env = (int)(tid / nin), k = (int)(tid % nin);
+  const T* s0 = s + ((size_t)env * ncol) * ns;
+  const T* sp = s + ((size_t)env * ncol + 1 + 2 * k) * ns;
+  const T* sm = s + ((size_t)env * ncol + 2 + 2 * k) * ns;
+  bool hp = valid[(size_t)env * ncol + 1 + 2 * k] != 0, hm = centered && valid[(size_t)env * ncol + 2 + 2 * k] != 0;
+  const T *a, *b; T den;
+  if (hp && hm) { a = sm; b = sp; den = 2 * eps; }
+  else if (hp) { a = s0; b = sp; den = eps; }
+  else if (hm) { a = sm; b = s0; den = eps; }
+  else { a = s0; b = s0; den = 1; }
+  T* Ce = C + (size_t)env * ns * nx;
+  T* De = D + (size_t)env * ns * nu;
+  for (int i = 0; i < ns; i++) {
+    T ds = (b[i] - a[i]) / den;
+    if (k < nx) Ce[(size_t)i * nx + k] = ds; else De[(size_t)i * nu + (k - nx)] = ds;
   }
 }
 

@@ -157,11 +157,14 @@ struct ObsSpecDev {
 // Point table of the finite-difference kernel (k_fd): point p = t * batch + e, t in [0, T), reads row (t, e) of each array at
 // base + t * step stride + e * env stride (+ i), device memory in the storage dtype TS, strides in elements (>= 0, 0 = broadcast;
 // checked against the allocations on the host, fd_highest_element in mjb_host.hpp).  Environment e's parameter rows apply.
-// A launch covers the slab of points [p0, p0 + npoint); its scratch (y_out, valid) is indexed by p - p0.
+// A launch covers the slab of points [p0, p0 + npoint); its scratch (y_out, valid, sens_out) is indexed by p - p0.
 struct FdPoints {
   const void *qpos, *qvel, *ctrl, *warmstart;   // warmstart null: zeros at every point
   long qpos_ss, qpos_es, qvel_ss, qvel_es, ctrl_ss, ctrl_es, ws_ss, ws_es;
   int p0, npoint;
+  // optional [npoint, ncol, nsensordata]: every column's sensordata (null: not stored).  LAST, so that the members before it sit where
+  // a kernel compiled before it existed reads them
+  double* sens_out;
 };
 
 struct StepArgs {

@@ -458,16 +458,23 @@ def mj_subtreeCoM(model: MjModel, data: MjData) -> None:
 
 
 def mjd_transitionFD(model: MjModel, data: MjData, eps: float, centered: bool, A, B, C=None, D=None, *unsupported) -> None:
-    """Batched finite-difference transition matrices (float64 on device)."""
+    """Batched finite-difference transition matrices (float64 on device).  ``C`` / ``D`` (``[nsensordata, 2nv]`` / ``[nsensordata, nu]``,
+    or with a leading batch axis like ``A`` and ``B``) receive the sensor Jacobians; the sensor path runs only when one of them is given."""
     if unsupported:
         raise TypeError("mjd_transitionFD takes 8 positional arguments")
     _check(model, data)
     data.push_host_edits()
-    Ab, Bb = data._sim.transition_fd(float(eps), bool(centered), copy=False)       # pinned views: copied once, into the caller's arrays
+    sensors = C is not None or D is not None
+    out = data._sim.transition_fd(float(eps), bool(centered), copy=False, sensors=sensors)   # pinned views: copied once, into the caller's arrays
+    Ab, Bb = out[0], out[1]
     if A is not None:
         A[...] = Ab[0] if A.ndim == 2 else Ab
     if B is not None and model.nu > 0:
         B[...] = Bb[0] if B.ndim == 2 else Bb
+    if C is not None and model.nsensordata > 0:
+        C[...] = out[2][0] if C.ndim == 2 else out[2]
+    if D is not None and model.nsensordata > 0 and model.nu > 0:
+        D[...] = out[3][0] if D.ndim == 2 else out[3]
 
 
 def _jac(model: MjModel, data: MjData, kind: int, idx: int, jacp, jacr) -> None:

@@ -148,7 +148,7 @@ def rollout(model: MjModel, data: MjData, control=None, *, initial_state=None, i
 
 
 def linearize_rollout(model: MjModel, data: MjData, control=None, *, initial_state=None, initial_warmstart=None, nstep: int | None = None,
-                      eps: float = 1e-6, centered: bool = True):
+                      eps: float = 1e-6, centered: bool = True, sensor_derivatives: bool = False):
     """``rollout`` plus the finite-difference transition matrices along the trajectory: ``(state, sensordata, A, B)`` with
     ``A [B, T, 2nv, 2nv]`` and ``B [B, T, 2nv, nu]`` float64 on the GPU.  ``(A[:, t], B[:, t])`` linearise step ``t``: they are taken
     at the state, the solver warm start and the control the rollout had BEFORE step ``t`` (``t = 0``: the initial ones) - identical to
@@ -159,7 +159,13 @@ def linearize_rollout(model: MjModel, data: MjData, control=None, *, initial_sta
     copy) and writes ``[T, B, ...]`` blocks, of which ``A`` and ``B`` are permuted views.  Arguments as for ``rollout``.  Nothing waits
     for the GPU (except the first call and a call with more points per slab than any before, which allocate the FD scratch).  The
     second submission is checked after the first has been enqueued: should it fail (device allocation of the scratch or the result
-    blocks), ``data`` is left in the rollout's final state and the exception is raised without (A, B)."""
+    blocks), ``data`` is left in the rollout's final state and the exception is raised without (A, B).
+
+    ``sensor_derivatives=True`` returns ``(state, sensordata, A, B, C, D)`` with the sensor Jacobians ``C [B, T, ns, 2nv]`` and
+    ``D [B, T, ns, nu]`` (``ns = nsensordata``; permuted views like ``A`` and ``B``, from ``mjb_transition_fd_points_sensors``):
+    ``C[:, t]`` and ``D[:, t]`` are the derivatives of ``sensordata[:, t]`` - the sensors of step ``t``'s forward pass - with respect to
+    the state before step ``t`` and its control, taken at the same point, warm start and control as ``(A[:, t], B[:, t])``.  The other
+    four results are bitwise those of the call without the flag."""
     import torch
 
     buf, nstep, time_col = _launch("linearize_rollout", model, data, control, initial_state, initial_warmstart, nstep, True, True)
@@ -173,9 +179,10 @@ def linearize_rollout(model: MjModel, data: MjData, control=None, *, initial_sta
         u = control[:nstep].unsqueeze(1).expand(nstep, B, nu)
     else:
         u = control.permute(1, 0, 2)[:nstep]
-    A, Bm = sim.transition_fd_points(pre[..., :nq], pre[..., nq:nq + nv], u, pre[..., time_col + 1:], eps=eps, centered=centered)
+    mats = sim.transition_fd_points(pre[..., :nq], pre[..., nq:nq + nv], u, pre[..., time_col + 1:], eps=eps, centered=centered,
+                                    sensors=bool(sensor_derivatives))
     state, sens = _results(buf[1:], time_col, 1 + nq + nv)
-    return state, sens, A.permute(1, 0, 2, 3), Bm.permute(1, 0, 2, 3)
+    return (state, sens, *(x.permute(1, 0, 2, 3) for x in mats))
 
 
 __all__ = ["rollout", "linearize_rollout"]

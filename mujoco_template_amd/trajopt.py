@@ -325,6 +325,47 @@ def solve_dare(data, A, B, Q, R, *, tol: float = 1e-12, max_iter: int = 32) -> D
     return DareResult(X, K, status, iters, change)
 
 
+class KalmanResult(NamedTuple):
+    P: object        # [nb, nx, nx] the steady-state a-priori error covariance, bitwise symmetric (zeros where status != 0)
+    L: object        # [nb, nx, ny] the gain of the one-step predictor (zeros where status != 0)
+    status: object   # [nb] int32, solve_dare's: 0 converged, 1 a Cholesky pivot (V or C P C' + V), 2 an LU pivot or an iterate not finite, 3 max_iter reached
+    iters: object    # [nb] int32 doubling iterations done
+    change: object   # [nb] relative change of the last iteration (+inf when not finite)
+
+
+def solve_kalman(data, A, C, W, V, *, tol: float = 1e-12, max_iter: int = 32) -> KalmanResult:
+    """Steady-state Kalman gain for ``nb`` systems ``x+ = A x + B u + w``, ``y = C x + D u + v`` with ``cov w = W``, ``cov v = V``, in
+    one kernel launch: the stabilising solution ``P`` (the steady-state a-priori error covariance) of
+
+        P = A P A' - A P C' (C P C' + V)^-1 C P A' + W        and        L = A P C' (C P C' + V)^-1
+
+    ``L`` is the gain of the one-step predictor ``xhat+ = A xhat + B du + L (dy - C xhat - D du)``, whose error dynamics are
+    ``A - L C``.  ``(A, B, C, D)`` are what ``linearize_rollout(..., sensor_derivatives=True)`` returns (the reference leaves ``C`` and
+    ``D`` of ``mjd_transitionFD`` out, mujoco_template/linearization.py:28-34).
+
+    The filter equation is the dual of the regulator's: this is ``solve_dare(data, A', C', W, V)`` with ``P = X`` and ``L = K'``, on the
+    same kernel (``mjb_lqr_dare``) - no new solver, nothing on the host.  The transposes cost one ``.transpose(-1, -2).contiguous()``
+    each; a block without a leading axis, shared by all systems, stays shared.
+
+    - The filter (measurement-update) gain:  ``M = torch.linalg.solve(C @ P @ C.mT + V, C @ P).mT``  ``= P C' (C P C' + V)^-1``.
+    - The stability check:  ``closed_loop_poles(data, A.mT, C.mT, L.mT).rho < 1``  (the poles of ``A' - C' L'``, those of ``A - L C``).
+
+    ``A [nb, nx, nx]``, ``C [nb, ny, nx]``, ``W [nb, nx, nx]``, ``V [nb, ny, ny]`` (``nx <= 64``, ``ny <= 32``), float64 on the data's GPU,
+    each optionally its trailing block alone; ``nb``, ``tol``, ``max_iter`` and ``status`` as in ``solve_dare``.  A pair ``(A, C)`` that is
+    not detectable ends with ``status != 0`` and zeros in ``P`` and ``L``, as ``solve_dare`` documents for a system that is not
+    stabilisable; no other system is affected."""
+    import torch
+
+    fn = "solve_kalman"
+    for name, x in (("A", A), ("C", C)):
+        if not isinstance(x, torch.Tensor) or x.ndim not in (2, 3):
+            raise ConfigError(f"{fn}: {name} must be a float64 torch tensor [nb, n, m] or [n, m]")
+    if A.shape[-1] != A.shape[-2] or C.shape[-1] != A.shape[-1]:
+        raise ConfigError(f"{fn}: A must be [nb, nx, nx] and C [nb, ny, nx], got {list(A.shape)} and {list(C.shape)}")
+    sol = solve_dare(data, A.transpose(-1, -2).contiguous(), C.transpose(-1, -2).contiguous(), W, V, tol=tol, max_iter=max_iter)
+    return KalmanResult(sol.X, sol.K.transpose(-1, -2), sol.status, sol.iters, sol.change)
+
+
 class PolesResult(NamedTuple):
     wr: object       # [nb, nx] real parts, by descending modulus, ties by descending wr, then descending wi (NaN where status != 0)
     wi: object       # [nb, nx] imaginary parts; a complex pair is two neighbours with equal wr and wi bitwise negated, the positive one first
@@ -646,4 +687,4 @@ def select_candidates(data, cost, cand, *, mode: str = "argmin", temperature=Non
     return TrajSelectResult(u, best, best_cost, weights)
 
 
-__all__ = ["LqrBackwardResult", "LqrBoxResult", "lqr_backward", "lqr_candidates", "DareResult", "solve_dare", "PolesResult", "closed_loop_poles", "TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]
+__all__ = ["LqrBackwardResult", "LqrBoxResult", "lqr_backward", "lqr_candidates", "DareResult", "solve_dare", "KalmanResult", "solve_kalman", "PolesResult", "closed_loop_poles", "TrajCostResult", "TrajSelectResult", "trajectory_cost", "select_candidates"]
